@@ -15,9 +15,16 @@ ghost-layer halo exchange and Krylov all-reduces over xGMI.  ``--workload cubeM`
 ``python bench.py --gpus N`` started WITHOUT a launcher (no WORLD_SIZE in the environment) starts its N ranks
 itself as child processes before anything touches the GPU; under ``python -m torch.distributed.run`` it is one rank.
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for the byte model of `roofline`).  The timed region
-is ``--steps`` timesteps between barriers; when that is shorter than ~0.5 s the bracket is repeated (the simulation
-simply continues) and the MEDIAN repetition is reported -- every repetition is listed under ``timing``.
+Prints ONE JSON line on rank 0.  A plain run sets up, runs ``--warmup`` untimed steps, times exactly ``--steps`` timesteps
+between barriers (``ms_per_step`` = that bracket / ``--steps``), writes the outputs if ``--dump-outputs DIR`` is given and
+prints the line.  ``--full`` adds everything the headline figure does not need (see DESIGN.md "Measurement" for the byte
+model of `roofline`): when the bracket is shorter than ~0.5 s it is repeated (the simulation simply continues) and the
+MEDIAN repetition is reported -- every repetition is listed under ``timing``; the SpMV roofline from HIP events in the timed
+region; the per-class pass; the out-of-cache ``roofline_large`` case; the CPU baseline and the parity of the GPU run against it.
+
+``--dump-outputs DIR`` writes what the last timed step computed -- the nodal fields a caller of ``SolverKNPEMI.step(i)``
+receives -- as ``DIR/<name>.npy`` (float64; ``<name>_rank<r>.npy`` with several ranks), at most 64 MB in all: beyond that
+every field is sampled at the same fixed, seeded set of vertices, written as ``DIR/sample_index.npy``.
 """
 from __future__ import annotations
 
@@ -45,6 +52,8 @@ PARITY_TOL = 1e-6         # north_star: potentials match the reference solve to 
 # (membrane terms only), so only the backward error is a meaningful gate there.
 TRUE_RES_TOL = 1e-5
 BACKWARD_TOL = 1e-8
+DUMP_MAX_BYTES = 64 << 20     # --dump-outputs: all files of all ranks together
+DUMP_SEED = 12345             # the vertex sample of an output beyond DUMP_MAX_BYTES
 
 
 def parse():
@@ -58,6 +67,11 @@ def parse():
     ap.add_argument("--pc", type=str, default="auto", help="auto (hypre-form AMG in 2D, btcc in 3D) | hypre | btcc | vbjacobi | none")
     ap.add_argument("--rtol", type=float, default=1e-9)
     ap.add_argument("--models", type=str, default="ci", help="ci (HH+ATP+cotransporters) | passive")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="write the fields computed by the last timed step to DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline figure does not need: repeated brackets, SpMV roofline, per-class pass, "
+                         "roofline_large, CPU baseline and parity (the options below apply to --full runs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=2)
     ap.add_argument("--no-parity-lu", action="store_true", help="parity leg: true residual only, skip the oracle's sparse direct solve "
@@ -69,7 +83,10 @@ def parse():
     ap.add_argument("--profile-all", action="store_true", help="time every kernel class with HIP events in the MAIN run (adds overhead)")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=VALUE",
                     help="override a ksp_settings entry (e.g. --set amg_cheby_degree=2); tuning runs only")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.profile_all and not args.full:
+        ap.error("--profile-all times the kernel classes of the main run: it needs --full")
+    return args
 
 
 # --------------------------------------------------------------------------------------------------------------
@@ -299,22 +316,58 @@ def problem_state(p):
     return st
 
 
+def output_arrays(p):
+    """What a caller of ``SolverKNPEMI.step(i)`` receives after the step: the nodal fields of both sides (concentrations and
+    potentials, ``wh``), the membrane potential and, with Hodgkin-Huxley membranes, the gating variables."""
+    out = {f.name: f.numpy() for side in p.wh for f in side}
+    out["phi_m"] = p.phi_m_prev.numpy()
+    for nm in ("n", "m", "h"):
+        f = getattr(p, nm, None)
+        if f is not None and hasattr(f, "numpy"):
+            out[nm] = f.numpy()
+    return out
+
+
+def dump_outputs(p, out_dir, rank, world):
+    """``--dump-outputs``: every array of ``output_arrays`` as float64 ``<name>.npy``; when they exceed this rank's share of
+    DUMP_MAX_BYTES, the same seeded sample of vertices of each (``sample_index.npy``, vertex numbers as float64)."""
+    import numpy as np
+    arrays = {k: np.asarray(v, dtype=np.float64).ravel() for k, v in output_arrays(p).items()}
+    n = {a.size for a in arrays.values()}
+    assert len(n) == 1, "the output fields are nodal fields of one mesh"
+    n = n.pop()
+    keep = min(n, (DUMP_MAX_BYTES // world) // (8 * (len(arrays) + 1)))      # + 1: the sample index
+    idx = None
+    if keep < n:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), v)
+    return {"dir": out_dir, "arrays": sorted(arrays), "n_vertices": int(n), "sampled": idx is not None, "dtype": "float64"}
+
+
 def main_case(args, world, rank, dist, torch):
-    """The headline measurement; returns (json dict, failure text or None, what the CPU baseline / parity legs need or None)."""
+    """The headline measurement; returns (json dict, failure text or None, what the CPU baseline / parity legs need or None).
+    A plain run times the ``--steps`` steps once with no events in them; ``--full`` adds the repetitions, the SpMV events of the
+    roofline, the per-class pass and the snapshot of the CPU legs."""
     # the parity snapshot is taken during warmup (never inside the timed region), at the last step the oracle sample covers
-    want_cpu = rank == 0 and world == 1 and not args.no_cpu_baseline
+    want_cpu = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
     snap_at = min(args.warmup, args.cpu_steps + 1) if want_cpu and args.warmup >= 1 else None
 
     case = build_case(args.workload, args, world, rank, args.warmup + args.steps * MAX_REPS)
     run = timed_run(case, args, world, dist, torch, args.steps, args.warmup, snapshot_at=snap_at,
-                    allow_repeat=not args.no_repeat, profile_mask=0x1f if args.profile_all else 0x1)
+                    allow_repeat=args.full and not args.no_repeat, profile_mask=(0x1f if args.profile_all else 0x1) if args.full else 0x0)
     be, solver = run["stepper"].be, case["solver"]
+    dumped = dump_outputs(case["problem"], args.dump_outputs, rank, world) if args.dump_outputs else None
     elapsed = run["elapsed"]
     n_dof = be.n_dof_global
     ms_per_step = 1e3 * elapsed / max(args.steps, 1)
     value = n_dof * args.steps / elapsed / 1e6
-    roof = roofline_block(be, run["prof"], args.workload, world)
-    classes = class_pass(run["stepper"], args, torch) if (world == 1 and args.class_steps > 0) else None
+    roof = roofline_block(be, run["prof"], args.workload, world) if args.full else None
+    classes = class_pass(run["stepper"], args, torch) if (args.full and world == 1 and args.class_steps > 0) else None
     norms = solver.potential_norms()
     n_steps_timed = len(run["its"])
     per_it = {k: run["stats"][k] / max(sum(run["its"]), 1) for k in ("allreduces", "halos", "readbacks", "norm_fallbacks")}
@@ -342,6 +395,7 @@ def main_case(args, world, rank, dist, torch):
         "kernel_classes": classes,
         "setup_s": run["setup_s"],
         "entry_point": "SolverKNPEMI.prepare() + SolverKNPEMI.step(i): the loop body of SolverKNPEMI.solve()",
+        "full": bool(args.full), "outputs": dumped,
     }
     fail = None
     if not out["config"]["converged_all"]:
@@ -405,7 +459,7 @@ def main():
 
     # ---- out-of-cache roofline: the 10^7-DoF-per-GPU point, same process, every kernel class timed with HIP events ----
     large = (args.large or "").lower()
-    if rank == 0 and world == 1 and large not in ("", "none") and large != args.workload:
+    if args.full and rank == 0 and world == 1 and large not in ("", "none") and large != args.workload:
         import gc
         gc.collect()
         torch.cuda.empty_cache()
