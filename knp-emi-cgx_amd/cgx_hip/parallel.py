@@ -50,6 +50,15 @@ class Comm:
         if self.size > 1:
             dist.barrier()
 
+    def bcast(self, obj, root=0):
+        """``MPI.Comm.bcast``: a picklable object from ``root`` to every rank (gloo on the host, NCCL through the rank's device)."""
+        if self.size == 1:
+            return obj
+        buf = [obj]
+        dev = torch.device("cuda", torch.cuda.current_device()) if self.backend == "nccl" else None
+        dist.broadcast_object_list(buf, src=root, device=dev)
+        return buf[0]
+
     def all_gather_object(self, obj):
         if self.size == 1:
             return [obj]

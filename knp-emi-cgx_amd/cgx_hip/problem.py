@@ -241,8 +241,9 @@ class MixedDimensionalProblem(ABC):
             self.initial_conditions = {}
             self.find_initial_conditions = False
         else:
-            raise NotImplementedError("Configs without 'initial_conditions' need the reference's 0-D ODE pre-processor "
-                                      "(membrane_ODE_systems.py), which is out of scope of the native hot path.")
+            # steady state of the 0-D membrane ODE system, found in set_initial_conditions (cgx_hip/membrane_odes.py)
+            self.initial_conditions = {}
+            self.find_initial_conditions = True
         if "membrane_data_tag" in config:
             self.membrane_data_tag = int(config["membrane_data_tag"])
         else:
@@ -397,6 +398,25 @@ class MixedDimensionalProblem(ABC):
                 vals = np.broadcast_to(fem.evaluate_numpy(integrand, env), xq.shape[:2])
                 val += float((fm[lo:lo + (1 << 19)][:, None] * vals * self.q_w[None, :]).sum())
         return self.comm.allreduce_sum(val)
+
+    def calculate_compartment_volumes_and_surface_areas(self):
+        """Volumes [m^3] of the neuronal, glial and extracellular spaces and areas [m^2] of the neuronal and glial membranes
+        (areas and lengths in 2D), summed over ranks (reference mixed_dim_problem.py:813-848: assemble_scalar(1*dx(tags)),
+        assemble_scalar(1*dS(tags)) with the membrane facet tags).  Cells are counted by the rank owning them, membrane
+        facets by the ownership rule of ``integrate_over_membrane``."""
+        lm = self.local_mesh
+        d = lm.coords.shape[1]
+        nco = int(lm.n_cells_owned)
+        X = lm.coords[lm.cells[:nco]]
+        vol = np.abs(np.linalg.det(X[:, 1:, :] - X[:, :1, :])) / math.factorial(d)
+        tags = lm.cell_tags[:nco]
+        volume = lambda t: self.comm.allreduce_sum(float(vol[np.isin(tags, t)].sum()))
+        self.vol_i_n = volume(self.neuron_tags)
+        self.area_g_n = self.integrate_over_membrane(1.0, self.neuron_tags)
+        self.vol_e = volume(self.extra_tag)
+        if self.glia_flag:
+            self.vol_i_g = volume(self.glia_tags)
+            self.area_g_g = self.integrate_over_membrane(1.0, self.glia_tags)
 
     # ---------------------------------------------------------------- backend plumbing
     def create_backend(self):
@@ -602,7 +622,10 @@ class ProblemKNPEMI(MixedDimensionalProblem):
                 self.wh[1][idx].x.array[:] = as_t(self._exact_nodal(ion["ke_init"]))
             self.print("Initial conditions set.")
             return
-        self.print("Setting initial conditions from input file ...")
+        if self.find_initial_conditions:
+            self.find_steady_state_initial_conditions()
+        else:
+            self.print("Setting initial conditions from input file ...")
         ic = self.initial_conditions
         if not self.glia_flag:
             self.phi_m_init.value = ic["phi_m"] if "phi_m" in ic else ic["phi_m_n"]
@@ -649,6 +672,34 @@ class ProblemKNPEMI(MixedDimensionalProblem):
                 self.print(f"Initial condition for {ion['name']}_i set to {ion['ki_init'].value}")
                 self.print(f"Initial condition for {ion['name']}_e set to {ion['ke_init'].value}")
         self.print("Initial conditions set.")
+
+    def find_steady_state_initial_conditions(self):
+        """KNPEMIx_problem.py:228-325: compartment measures on every rank, the membrane ODE system solved to steady state
+        on rank 0, the state broadcast.  Fills ``initial_conditions`` under the YAML key names (the state names of the ODE
+        system) and records the wall time in ``ic_solve_s``."""
+        from .membrane_odes import ThreeCompartmentMembraneODESystem, TwoCompartmentMembraneODESystem
+        self.print("Solving ODE system to find steady-state initial conditions ...")
+        tic = time.perf_counter()
+        self.calculate_compartment_volumes_and_surface_areas()
+        areas = (self.area_g_n, self.area_g_g) if self.glia_flag else (self.area_g_n,)
+        if not min(areas) > 0:
+            raise RuntimeError("Steady-state initial conditions: no membrane facet carries a neuron" + (" or glia" if self.glia_flag else "")
+                               + " tag (membrane tags must be the cell tags); provide 'initial_conditions' in the input file.")
+        cls = ThreeCompartmentMembraneODESystem if self.glia_flag else TwoCompartmentMembraneODESystem
+        odes = cls(self, plot_show=False, plot_save=False, stimulus_flag=False)
+        state = None
+        if self.comm.rank == 0:
+            try:
+                state = odes.solve_ode_system()
+            except Exception as e:          # noqa: BLE001 -- reported on every rank below, not swallowed
+                state = f"{type(e).__name__}: {e}"
+        state = self.comm.bcast(state, root=0)
+        if isinstance(state, str):
+            raise RuntimeError(state)
+        self.initial_conditions = dict(zip(cls.state_names, (float(v) for v in state)))
+        self.ic_solve_s = time.perf_counter() - tic
+        self.print(f"Steady-state initial conditions found in {self.ic_solve_s:0.3f} seconds: "
+                   + ", ".join(f"{k} = {v:.10g}" for k, v in self.initial_conditions.items()))
 
     # ---- "variational form": compile the membrane currents (KNPEMIx_problem.py:504-555)
     def setup_variational_form(self):
