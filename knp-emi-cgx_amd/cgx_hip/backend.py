@@ -597,10 +597,11 @@ class Backend:
 
     def stats(self):
         """||B b|| of the last solve and the exchange / read-back counters since the last ``profile_reset``."""
-        out = (C.c_double * 8)()
+        out = (C.c_double * 9)()   # KNP_ST_COUNT
         self.check(self.lib.knp_get_stats(self.ctx, out))
         return {"bnorm": out[0], "allreduces": int(out[1]), "halos": int(out[2]), "readbacks": int(out[3]), "fused": int(out[4]),
-                "norm_fallbacks": int(out[5]), "blocked": int(out[6]), "fused_levels": int(out[7])}
+                "norm_fallbacks": int(out[5]), "blocked": int(out[6]), "fused_levels": int(out[7]),
+                "fused_dots": int(out[8])}
 
     def traffic_model(self):
         """bytes one application of each kernel class must move (knp_get_traffic_model)"""

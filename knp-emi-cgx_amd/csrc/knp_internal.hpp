@@ -270,6 +270,7 @@ struct knp_ctx {
     bool have_sources = false;
     // preconditioner
     int pc_kind = KNP_PC_NONE;
+    int fused_dots = 1;       // first reduction stage in the cycle's last leg (KNP_FUSED_DOTS=0: off)
     double* d_vbj = nullptr;  // [n_nodes_owned*16] compact vertex blocks
     KnpAmgHier hier[KNP_MAX_HIER];   // 0: all fields (block-Jacobi form) or ion fields; 1: potential
     int amg_fp32 = 0;                // store the preconditioner's operators in fp32 (vectors and A stay fp64)
@@ -346,6 +347,7 @@ struct knp_ctx {
     // statistics of the solves (knp_get_stats): ||B b|| of the last solve, exchanges and host read-backs since the last reset
     double last_bnorm = 0.0;
     int64_t n_allreduce = 0, n_halo = 0, n_readback = 0;
+    int64_t n_fused_dots = 0;   // reductions whose first stage ran in the cycle's last leg (KNP_FUSED_DOTS)
     // step timers (knp_timer_mark / knp_timer_read): timing events recorded on the main stream, read back in one go
     std::vector<hipEvent_t> tm_events;
     size_t tm_used = 0;

@@ -1444,6 +1444,12 @@ k_bresidual(int n_rows, const int32_t* __restrict__ rp, const float4* __restrict
         }
     }
 }
+// the x0 + c2 Dinv r part of k_blevel_up's row i (one definition: the leg with the reduction in its epilogue writes the same z)
+__device__ __forceinline__ double bup_base(const double* __restrict__ dinv, const double* __restrict__ b, const double* __restrict__ r,
+                                           const double* xin, double c, double c2, size_t i) {
+    const double di = dinv[i];
+    return (xin ? xin[i] : c * di * b[i]) + c2 * di * r[i];
+}
 // z = x0 + c2 Dinv r + S xc for the NF unknowns of every node row; x0 = xin when given, else c Dinv b.  RS = unknowns per ROW node
 // in dinv, b, r, xin, z (4 on level 0 -- the fourth one, the potential, is not touched when NF == 3)
 template <int L, int NF, int RS>
@@ -1460,11 +1466,7 @@ k_blevel_up(int n_rows, const int32_t* __restrict__ rp, const float4* __restrict
     if (row < n_rows) {
         if (fin) {   // the epilogue's operands travel together with the gathers
 #pragma unroll
-            for (int k = 0; k < KL; ++k) {
-                const size_t i = (size_t)RS * row + (L >= NF ? lane : k);
-                const double di = dinv[i];
-                base[k] = (xin ? xin[i] : c * di * b[i]) + c2 * di * r[i];
-            }
+            for (int k = 0; k < KL; ++k) base[k] = bup_base(dinv, b, r, xin, c, c2, (size_t)RS * row + (L >= NF ? lane : k));
         }
         brow_dot<L, NF, NF>(rp[row], rp[row + 1], lane, ev, ci, xc, s);
     }
@@ -1517,6 +1519,132 @@ static void launch_blevel_up(hipStream_t st, int nf, int rs, const KnpBlockedCsr
     if (nf == 4) launch_blevel_up_t<4, 4>(st, M, xc, dinv, b, r, xin, c, c2, z);
     else if (rs == 4) launch_blevel_up_t<3, 4>(st, M, xc, dinv, b, r, xin, c, c2, z);
     else launch_blevel_up_t<3, 3>(st, M, xc, dinv, b, r, xin, c, c2, z);
+}
+
+// ---- the last leg of the cycle with the first stage of a GMRES reduction in its epilogue (KNP_FUSED_DOTS) -------------------------
+// A caller that reduces z = B r right after the cycle (k_multi_dot<8, NS, true>: V_i.z, the sum of the potential entries, z.z) passes
+// a DotReq; a cycle that ends in the node-blocked level-0 leg on four unknowns per node computes those partial sums while z is in
+// registers, in k_multi_dot's rows (V_0..V_{m-1} [, potential sum], z.z) but with row stride RED_WIDE (partial[row * RED_WIDE + blk]),
+// and reports the number of partial blocks it wrote.  Otherwise `done` stays false and the caller runs k_multi_dot.
+static constexpr int BU_MAX_M = 8;
+struct DotReq {
+    int m;                // basis vectors V_0 .. V_{m-1} (<= BU_MAX_M)
+    bool ns;              // also the sum of the potential entries
+    int64_t ldv;
+    const double* V;
+    double* partial;
+    bool done = false;
+    int nb = 0;           // partial blocks written, in rows of RED_WIDE (k_reduce_fin takes the row stride)
+};
+static constexpr int RED_WIDE = 4096;   // row stride of the leg's partial sums: (BU_MAX_M + 2) rows fit the RED_SLOTS x RED_BLOCKS buffer
+static_assert((BU_MAX_M + 2) * RED_WIDE <= RED_SLOTS * RED_BLOCKS, "partial-sum buffer");
+// z as k_blevel_up<L, 4, 4> on the same grid (one row tile of NT threads per block, 2 064 blocks at 512^2), so its partial sums come
+// in rows of RED_WIDE blocks (see DotReq).  Measured on MI355X: squeezing the leg into RED_BLOCKS blocks costs more than the launch it
+// saves -- a grid-stride loop over tiles needs 11 more VGPRs (one wave per SIMD less), 576-thread tiles leave a tail of whole blocks
+// (25 vs 17 us).  One lane per unknown (L >= 4) or one per node (L == 2) adds its z entries in.
+// G >= m: basis vectors whose entries are loaded at once, right behind the gathers (one memory round trip for all of them, not m).
+template <int L, bool NS, int G>
+__global__ void __launch_bounds__(NT)
+k_blevel_up_dots(int n_rows, const int32_t* __restrict__ rp, const float4* __restrict__ ev, const int32_t* __restrict__ ci,
+                 const double* __restrict__ xc, const double* __restrict__ dinv, const double* __restrict__ b, const double* __restrict__ r,
+                 const double* xin, double c, double c2, double* z, int m, int64_t ldv, const double* __restrict__ V, double* __restrict__ partial) {
+    constexpr int NF = 4, KL = L >= NF ? 1 : NF, MAX_NW = NT / 64;
+    // sm[v * MAX_NW + wave]: wave `wave`'s sum of value v (V_0.z .. V_{m-1}.z [, potential sum], z.z)
+    __shared__ double sm[(BU_MAX_M + 2) * MAX_NW];
+    const int lane = threadIdx.x & (L - 1);
+    const int wave = threadIdx.x >> 6, wl = threadIdx.x & 63;
+    const int nv = m + (NS ? 1 : 0) + 1;
+    {
+        const int row = (blockIdx.x * NT + threadIdx.x) / L;
+        const bool fin = row < n_rows && (L >= NF ? lane < NF : lane == 0);
+        double s[4] = {0.0, 0.0, 0.0, 0.0};
+        double base[KL];
+        if (row < n_rows) {
+            if (fin) {
+#pragma unroll
+                for (int k = 0; k < KL; ++k) base[k] = bup_base(dinv, b, r, xin, c, c2, (size_t)NF * row + (L >= NF ? lane : k));
+            }
+            brow_dot<L, NF, NF>(rp[row], rp[row + 1], lane, ev, ci, xc, s);
+        }
+        double vv[G][KL];   // this lane's entries of V_0 .. V_{m-1}: in flight during the butterfly and the epilogue
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            if (g < m && fin) {
+                const double* vg = V + (int64_t)g * ldv + (size_t)NF * row;
+                if constexpr (KL == 4) {   // the node's 32 bytes of V_g as two 16-byte loads
+                    const double2 v0 = *reinterpret_cast<const double2*>(vg);
+                    const double2 v1 = *reinterpret_cast<const double2*>(vg + 2);
+                    vv[g][0] = v0.x; vv[g][1] = v0.y; vv[g][2] = v1.x; vv[g][3] = v1.y;
+                } else {
+                    vv[g][0] = vg[lane];
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < KL; ++k) vv[g][k] = 0.0;
+            }
+        }
+        breduce<L, NF>(s);
+        // the row's contributions (zero outside the finishing lanes), summed over the wave
+        double zv[KL], pns = 0.0, pww = 0.0;
+#pragma unroll
+        for (int k = 0; k < KL; ++k) zv[k] = 0.0;
+        if (fin) {
+#pragma unroll
+            for (int k = 0; k < KL; ++k) {
+                const int f = L >= NF ? lane : k;
+                zv[k] = base[k] + bpick<NF>(s, f);
+                z[(size_t)NF * row + f] = zv[k];
+                if (NS && f == 3) pns += zv[k];   // (the potential: fourth unknown of the node)
+                pww += zv[k] * zv[k];
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+            if (g >= m) break;   // (uniform)
+            double p = 0.0;
+#pragma unroll
+            for (int k = 0; k < KL; ++k) p += vv[g][k] * zv[k];
+            const double t = wave_sum(p);
+            if (wl == 0) sm[g * MAX_NW + wave] = t;
+        }
+        if (NS) {
+            const double t = wave_sum(pns);
+            if (wl == 0) sm[m * MAX_NW + wave] = t;
+        }
+        const double t = wave_sum(pww);
+        if (wl == 0) sm[(nv - 1) * MAX_NW + wave] = t;
+    }
+    // block sums: thread v adds value v of the waves in wave order
+    __syncthreads();
+    if (threadIdx.x < nv) {
+        double t = 0.0;
+#pragma unroll
+        for (int w = 0; w < MAX_NW; ++w) t += sm[threadIdx.x * MAX_NW + w];
+        partial[(size_t)threadIdx.x * RED_WIDE + blockIdx.x] = t;
+    }
+}
+// z (and the partial sums of `dq`) from the node-blocked level-0 leg on four unknowns per node; false when the request cannot be
+// taken here (more than RED_WIDE blocks: the bandwidth-bound sizes, where a launch less does not matter; the plain leg then runs)
+static bool launch_blevel_up_dots(knp_ctx* ctx, hipStream_t st, const KnpBlockedCsr& M, const double* xc, const double* dinv, const double* b,
+                                  const double* r, double c, double c2, double* z, DotReq* dq) {
+    const int lanes = M.lanes == 2 || M.lanes == 4 || M.lanes == 8 || M.lanes == 16 ? M.lanes : 32;   // as KNP_BL_SWITCH
+    const int64_t threads = (int64_t)M.n_rows * lanes;
+    if (M.n_rows <= 0 || dq->m < 0 || dq->m > BU_MAX_M || threads > (int64_t)RED_WIDE * NT) return false;
+    const int nbd = nblocks(threads, NT);
+#define KNP_BUD_G(LL, NS_, G_) hipLaunchKernelGGL((k_blevel_up_dots<LL, NS_, G_>), dim3(nbd), dim3(NT), 0, st, M.n_rows, M.rp, M.ev, M.ci, xc, dinv, b, r, \
+                                              (const double*)nullptr, c, c2, z, dq->m, dq->ldv, dq->V, dq->partial)
+#define KNP_BUD(LL)                                                                            \
+    do {                                                                                       \
+        if (dq->m <= 3) { if (dq->ns) KNP_BUD_G(LL, true, 3); else KNP_BUD_G(LL, false, 3); } \
+        else { if (dq->ns) KNP_BUD_G(LL, true, 8); else KNP_BUD_G(LL, false, 8); }            \
+    } while (0)
+    KNP_BL_SWITCH(M.lanes, KNP_BUD)
+#undef KNP_BUD
+#undef KNP_BUD_G
+    dq->done = true;
+    dq->nb = nbd;
+    ++ctx->n_fused_dots;
+    return true;
 }
 
 // setup helpers of the fused cycle
@@ -1661,26 +1789,33 @@ __device__ __forceinline__ void proj_norm_body(double s, double ww, double* __re
 // single-block kernel instead of k_reduce_partials + k_givens (or + k_proj_norm) -- one launch at the ~4.5 us floor less per GMRES
 // iteration and per norm.  One wave per row, 16 partial sums per lane, fixed order: deterministic.
 //   mode 1: Givens step of iteration j on red[slot0 .. slot0 + nred)      mode 2: gauge-projected norm from {s, w.w}
-__global__ void __launch_bounds__(NT)
-k_reduce_fin(int mode, int nb, int nred, const double* __restrict__ partial, double* __restrict__ red, int slot0, GmLayout L, int j, int has_ns,
-             double inv_cnt, double* __restrict__ gm, int slot_out, double cancel, double* mirror, volatile int64_t* seq, int64_t seq_val) {
-    __shared__ double s_red[RED_SLOTS];
-    static_assert(RED_BLOCKS == 1024, "k_reduce_fin: 16 partial sums per lane");
+// s_red[row] = sum_b partial[row * stride + b] for row < nred, b < nb (followed by a barrier): one wave per row, 16 partial sums
+// per lane and chunk of 1024, fixed order -- the same values in every block that calls it
+__device__ __forceinline__ void reduce_partial_rows(int nb, int nred, const double* __restrict__ partial, int stride, double* s_red) {
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int row = wave; row < nred; row += NT / 64) {
-        double v[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int b = lane + 64 * k;
-            v[k] = b < nb ? partial[(size_t)row * RED_BLOCKS + b] : 0.0;
-        }
         double a = 0.0;
+        for (int c = 0; c < nb; c += 1024) {
+            double v[16];
 #pragma unroll
-        for (int k = 0; k < 16; ++k) a += v[k];
+            for (int k = 0; k < 16; ++k) {
+                const int b = c + lane + 64 * k;
+                v[k] = b < nb ? partial[(size_t)row * stride + b] : 0.0;
+            }
+#pragma unroll
+            for (int k = 0; k < 16; ++k) a += v[k];
+        }
         a = wave_sum(a);
         if (lane == 0) s_red[row] = a;
     }
     __syncthreads();
+}
+__global__ void __launch_bounds__(NT)
+k_reduce_fin(int mode, int nb, int nred, const double* __restrict__ partial, double* __restrict__ red, int slot0, GmLayout L, int j, int has_ns,
+             double inv_cnt, double* __restrict__ gm, int slot_out, double cancel, double* mirror, volatile int64_t* seq, int64_t seq_val,
+             int stride = RED_BLOCKS) {
+    __shared__ double s_red[RED_SLOTS];
+    reduce_partial_rows(nb, nred, partial, stride, s_red);
     if (threadIdx.x < nred) red[slot0 + threadIdx.x] = s_red[threadIdx.x];
     if (threadIdx.x == 0) {
         if (mode == 1) givens_body(L, j, has_ns, inv_cnt, s_red, -1, gm, mirror, seq, seq_val);
@@ -3012,7 +3147,10 @@ static int check_fields(knp_ctx* ctx, const knp_fields* f, bool need_phim) {
 }
 
 // cc = psi / (sum_j z_j^2 k_j) / M_lumped at every owned node (Schur term of the block-triangular preconditioner)
+// Only the block-triangular forms read cc (k_level_up MODE 1, k_schur_fin): skipped for the kinds that never do.  Before knp_pc_setup
+// (kind NONE) it is written, so that a block-triangular setup after the first assembly finds it.
 static void launch_schur_diag(knp_ctx* ctx, const FieldPtrs& f) {
+    if (ctx->pc_kind == KNP_PC_AMG || ctx->pc_kind == KNP_PC_VBJACOBI) { ctx->have_cc = false; return; }
     const KnpHostGraph& g = ctx->g;
     hipLaunchKernelGGL(k_schur_diag, dim3(nblocks(g.n_nodes_owned)), dim3(NT), 0, ctx->stream, g.n_nodes_owned, ctx->psi, ctx->z[0], ctx->z[1],
                        ctx->z[2], ctx->d_node_vertex, ctx->d_node_side, f, ctx->d_ML, ctx->d_cc);
@@ -4114,7 +4252,8 @@ static bool fused_eligible(const knp_ctx* ctx, const KnpAmgHier& H) {
 
 // z (level-0 rows of this hierarchy) = V-cycle applied to b.  Potential-only hierarchies (native0 == 3) take b on compact
 // node-indexed vectors and write z[4 node + 3] = cycle + cc[node] * b[node] (Schur term); the others work on 4 unknowns per node.
-static void amg_cycle_fused(knp_ctx* ctx, KnpAmgHier& H, const double* b, double* z) {
+// dq: the caller's reduction of z (see DotReq), taken by the node-blocked cycle on four unknowns per node
+static void amg_cycle_fused(knp_ctx* ctx, KnpAmgHier& H, const double* b, double* z, DotReq* dq = nullptr) {
     hipStream_t st = ctx->stream;
     const int nl = H.levels;
     const bool phi = H.native0 == 3;
@@ -4146,6 +4285,9 @@ static void amg_cycle_fused(knp_ctx* ctx, KnpAmgHier& H, const double* b, double
         if (H.cinv_f) launch_dense_matvec<float>(st, H.nc, H.cinv_f, cf_b(nl - 1), cf_x(nl - 1));
         else launch_dense_matvec<double>(st, H.nc, H.cinv, cf_b(nl - 1), cf_x(nl - 1));
         for (int l = nl - 2; l >= 1; --l) launch_brestrict(st, nf, nf, H.lv[l].bU, H.lv[l].cat, cf_x(l), 0.0, nullptr, nullptr, nullptr);
+        if (dq && nf == 4 && 4 * (int64_t)L0.bS.n_rows == ctx->n_dof_owned &&
+            launch_blevel_up_dots(ctx, st, L0.bS, cf_x(1), L0.inv_diag, b, L0.r, c0, c0, z, dq))
+            return;
         launch_blevel_up(st, nf, 4, L0.bS, cf_x(1), L0.inv_diag, b, L0.r, nullptr, c0, c0, z);
         return;
     }
@@ -4281,6 +4423,7 @@ int knp_pc_setup(knp_ctx* ctx, int32_t kind) {
         }
     }
     ctx->pc_kind = kind;
+    ctx->fused_dots = !(getenv("KNP_FUSED_DOTS") && atoi(getenv("KNP_FUSED_DOTS")) == 0);   // read at every knp_pc_setup, like KNP_FUSED
     for (int h = 0; h < KNP_MAX_HIER; ++h) ctx->hier[h].fused = 0;
     if (kind == KNP_PC_AMG) ctx->hier[0].fused = fused_eligible(ctx, ctx->hier[0]) ? 1 : 0;
     if (kind == KNP_PC_AMG_BT || kind == KNP_PC_AMG_LT) {   // both or none: the potential hierarchy then works on compact vectors
@@ -4371,8 +4514,11 @@ __global__ void __launch_bounds__(NT) k_bc_copy(int n_bc, const int32_t* __restr
     }
 }
 
-static int pc_apply_proj(knp_ctx* ctx, const double* r, double* z, int64_t cnt) {
+// dq (optional): the reduction the caller runs on z next -- taken by the cycle when nothing below changes z after it (no deflation,
+// Dirichlet rows or projection, one GPU); dq->done tells the caller
+static int pc_apply_proj(knp_ctx* ctx, const double* r, double* z, int64_t cnt, DotReq* dq = nullptr) {
     const int dm = ctx->defl_m;
+    if (dq && (dm > 0 || ctx->n_bc > 0 || (ctx->ns_on && cnt > 0) || ctx->allreduce || ctx->p2p)) dq = nullptr;
     if (dm > 0) {   // coarse sums of the input residual (before r is possibly overwritten)
         ProfScope ps(ctx, 4);
         const int no = ctx->g.n_nodes_owned;
@@ -4392,7 +4538,7 @@ static int pc_apply_proj(knp_ctx* ctx, const double* r, double* z, int64_t cnt) 
                                    ctx->d_node_side, ctx->d_node_gv, ctx->d_gv_node_e, ctx->d_vbj, r, z);
                 break;
             case KNP_PC_AMG: {
-                if (ctx->hier[0].fused) { amg_cycle_fused(ctx, ctx->hier[0], r, z); break; }
+                if (ctx->hier[0].fused) { amg_cycle_fused(ctx, ctx->hier[0], r, z, dq); break; }
                 double* out = amg_vcycle(ctx, ctx->hier[0], 0, r, z);
                 if (out != z) HIPCHK(hipMemcpyAsync(z, out, (size_t)ctx->n_dof_owned * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
                 break;
@@ -4401,7 +4547,11 @@ static int pc_apply_proj(knp_ctx* ctx, const double* r, double* z, int64_t cnt) 
             case KNP_PC_AMG_LT: {
                 // z_k = V_k r_k ; t_phi = r_phi - A_{phi k} z_k ; z_phi = V_phi t_phi + cc * t_phi   (LT: literal coupling, no cc term)
                 const bool lit = ctx->pc_kind == KNP_PC_AMG_LT;
-                if (!ctx->have_A || !ctx->have_cc) { ctx->err = "block-triangular preconditioner needs an assembled matrix"; return KNP_E_STATE; }
+                if (!ctx->have_A) { ctx->err = "block-triangular preconditioner needs an assembled matrix"; return KNP_E_STATE; }
+                if (!ctx->have_cc) {   // (launch_schur_diag skips it while another kind is set up)
+                    ctx->err = "block-triangular preconditioner needs the Schur diagonal: assemble the right-hand side or the matrix after knp_pc_setup";
+                    return KNP_E_STATE;
+                }
                 if (ctx->hier[0].fused) {
                     amg_cycle_fused(ctx, ctx->hier[0], r, z);                 // ion entries of z
                     if (lit) launch_phi_rhs_literal<true>(ctx, r, z, ctx->d_t2);
@@ -4519,14 +4669,17 @@ static bool fused_norm_possible(const knp_ctx* ctx, int64_t cnt) {
 static int pc_apply_norm(knp_ctx* ctx, const double* r, double* z, int64_t cnt, bool* fused, bool side = false) {
     if (side) {
         *fused = true;
-        KCHK(pc_apply_proj(ctx, r, z, 0));
+        DotReq dq{0, true, (int64_t)ctx->n_dof_local, ctx->d_V, ctx->d_partial_s};
+        KCHK(pc_apply_proj(ctx, r, z, 0, (ctx->fused_dots && fin_ok(ctx)) ? &dq : nullptr));   // (as the in-line form below)
         ProfScope ps(ctx, 1);
-        const int nb = ctx->n_red_blocks;
-        hipLaunchKernelGGL((k_multi_dot<8, true, true>), dim3(nb), dim3(NT), 0, ctx->stream, ctx->n_dof_owned, (int64_t)ctx->n_dof_local, 0, 0,
-                           ctx->d_V, z, ctx->d_partial_s);
+        const int nb = dq.done ? dq.nb : ctx->n_red_blocks;
+        if (!dq.done)
+            hipLaunchKernelGGL((k_multi_dot<8, true, true>), dim3(nb), dim3(NT), 0, ctx->stream, ctx->n_dof_owned, (int64_t)ctx->n_dof_local, 0, 0,
+                               ctx->d_V, z, ctx->d_partial_s);
         ++ctx->n_allreduce;
         hipLaunchKernelGGL(k_reduce_fin, dim3(1), dim3(NT), 0, ctx->stream, 2, nb, 2, ctx->d_partial_s, ctx->d_red, SIDE_SLOT + 2, GmLayout{1}, 0, 0,
-                           1.0 / (double)cnt, (double*)nullptr, SIDE_SLOT, GM_CANCEL, ctx->mirror(), (volatile int64_t*)nullptr, (int64_t)0);
+                           1.0 / (double)cnt, (double*)nullptr, SIDE_SLOT, GM_CANCEL, ctx->mirror(), (volatile int64_t*)nullptr, (int64_t)0,
+                           dq.done ? RED_WIDE : RED_BLOCKS);
         HIPCHK(hipGetLastError());
         return KNP_OK;
     }
@@ -4536,15 +4689,18 @@ static int pc_apply_norm(knp_ctx* ctx, const double* r, double* z, int64_t cnt, 
         return dot_to_slot(ctx, z, z, 60);
     }
     *fused = true;
-    KCHK(pc_apply_proj(ctx, r, z, 0));
+    DotReq dq{0, true, (int64_t)ctx->n_dof_local, ctx->d_V, ctx->d_partial};
+    KCHK(pc_apply_proj(ctx, r, z, 0, (ctx->fused_dots && fin_ok(ctx)) ? &dq : nullptr));   // (k_reduce_partials takes no stride)
     ProfScope ps(ctx, 1);
-    const int nb = ctx->n_red_blocks;
-    hipLaunchKernelGGL((k_multi_dot<8, true, true>), dim3(nb), dim3(NT), 0, ctx->stream, ctx->n_dof_owned, (int64_t)ctx->n_dof_local, 0, 0,
-                       ctx->d_V, z, ctx->d_partial);
+    const int nb = dq.done ? dq.nb : ctx->n_red_blocks;
+    if (!dq.done)
+        hipLaunchKernelGGL((k_multi_dot<8, true, true>), dim3(nb), dim3(NT), 0, ctx->stream, ctx->n_dof_owned, (int64_t)ctx->n_dof_local, 0, 0,
+                           ctx->d_V, z, ctx->d_partial);
     if (fin_ok(ctx)) {
         ++ctx->n_allreduce;
         hipLaunchKernelGGL(k_reduce_fin, dim3(1), dim3(NT), 0, ctx->stream, 2, nb, 2, ctx->d_partial, ctx->d_red, 62, GmLayout{1}, 0, 0, 1.0 / (double)cnt,
-                           (double*)nullptr, 60, GM_CANCEL, ctx->mirror(), ctx->mirror() ? ctx->h_seq_dev : nullptr, ++ctx->seq_counter);
+                           (double*)nullptr, 60, GM_CANCEL, ctx->mirror(), ctx->mirror() ? ctx->h_seq_dev : nullptr, ++ctx->seq_counter,
+                           dq.done ? RED_WIDE : RED_BLOCKS);
         HIPCHK(hipGetLastError());
         return KNP_OK;
     }
@@ -4807,13 +4963,17 @@ int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doubl
             // The null-space removal that follows the preconditioner (KSP_RemoveNullSpace) is folded into the
             // Gram-Schmidt pass: the basis vectors are orthogonal to ns, so h_i = V_i.(w - ns ns.w) = V_i.w, and the
             // projection itself is one more "basis vector" in the update (same reduction, no extra all-reduce).
-            KCHK(pc_apply_proj(ctx, ctx->d_t, ctx->d_w, ns ? 0 : cnt));
+            // ONE reduction per iteration: the j+1 Gram-Schmidt coefficients, the gauge coefficient and w.w; the norm of the
+            // orthogonalised vector follows by Pythagoras (explicit norm only when that would cancel, see k_givens).  Its first stage
+            // runs in the preconditioner's last leg where that can take it (DotReq), else in k_multi_dot.
+            DotReq dq{j + 1, ns, ldv, ctx->d_V, ctx->d_partial};
+            KCHK(pc_apply_proj(ctx, ctx->d_t, ctx->d_w, ns ? 0 : cnt, (ctx->fused_dots && fin_ok(ctx) && j + 1 <= BU_MAX_M) ? &dq : nullptr));
             int flag = 0;
             {
                 ProfScope ps(ctx, 1);
-                // ONE reduction per iteration: the j+1 Gram-Schmidt coefficients, the gauge coefficient and w.w; the norm of the
-                // orthogonalised vector follows by Pythagoras (explicit norm only when that would cancel, see k_givens)
-                for (int i0 = 0; i0 <= j; i0 += 8) {
+                const int nbr = dq.done ? dq.nb : nb;   // partial blocks of the first stage, and their row stride
+                const int pst = dq.done ? RED_WIDE : RED_BLOCKS;
+                for (int i0 = 0; i0 <= j && !dq.done; i0 += 8) {
                     if (i0 == 0 && ns)
                         hipLaunchKernelGGL((k_multi_dot<8, true, true>), dim3(nb), dim3(NT), 0, st, n, ldv, i0, j + 1, ctx->d_V, ctx->d_w, ctx->d_partial);
                     else if (i0 == 0)
@@ -4824,10 +4984,11 @@ int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doubl
                 const int nred = j + 2 + nsi;
                 if (fin_ok(ctx)) {   // one GPU: second reduction stage + Givens step in one single-block kernel
                     ++ctx->n_allreduce;
-                    hipLaunchKernelGGL(k_reduce_fin, dim3(1), dim3(NT), 0, st, 1, nb, nred, ctx->d_partial, ctx->d_red, 0, GL, j, nsi, ns ? 1.0 / (double)cnt : 0.0, gm,
-                                       0, 0.0, ctx->mirror() ? ctx->h_red_dev + GM_RES : nullptr, ctx->mirror() ? ctx->h_seq_dev : nullptr, ++ctx->seq_counter);
+                    hipLaunchKernelGGL(k_reduce_fin, dim3(1), dim3(NT), 0, st, 1, nbr, nred, ctx->d_partial, ctx->d_red, 0, GL, j, nsi, ns ? 1.0 / (double)cnt : 0.0, gm,
+                                       0, 0.0, ctx->mirror() ? ctx->h_red_dev + GM_RES : nullptr, ctx->mirror() ? ctx->h_seq_dev : nullptr, ++ctx->seq_counter,
+                                       pst);
                 } else {
-                    hipLaunchKernelGGL(k_reduce_partials, dim3(nred), dim3(NT), 0, st, nb, ctx->d_partial, ctx->d_red, 0, (double*)nullptr);
+                    hipLaunchKernelGGL(k_reduce_partials, dim3(nred), dim3(NT), 0, st, nbr, ctx->d_partial, ctx->d_red, 0, (double*)nullptr);
                     KCHK(allreduce_slots(ctx, 0, nred));
                     hipLaunchKernelGGL(k_givens, dim3(1), dim3(64), 0, st, GL, j, nsi, ns ? 1.0 / (double)cnt : 0.0, ctx->d_red, -1, gm,
                                        ctx->mirror() ? ctx->h_red_dev + GM_RES : nullptr, ctx->mirror() ? ctx->h_seq_dev : nullptr, ++ctx->seq_counter);
@@ -4994,6 +5155,7 @@ int knp_profile_reset(knp_ctx* ctx) {
     KCHK(prof_collect(ctx));
     for (int i = 0; i < KNP_NPROF; ++i) { ctx->prof_ms[i] = 0; ctx->prof_n[i] = 0; }
     ctx->n_allreduce = ctx->n_halo = ctx->n_readback = ctx->n_norm_fallback = 0;
+    ctx->n_fused_dots = 0;
     return KNP_OK;
 }
 // Bytes the kernels of one application must move, from the sizes of the arrays they read and write (the "algorithmic bytes" of the
@@ -5070,6 +5232,7 @@ int knp_get_stats(const knp_ctx* ctx, double* out) {
     for (int h = 0; h < KNP_MAX_HIER; ++h)
         for (int l = 1; l < ctx->hier[h].levels; ++l) nlf += ctx->hier[h].lv[l].lfused;
     out[KNP_ST_FUSED_LEVELS] = (double)nlf;
+    out[KNP_ST_FUSED_DOTS] = (double)ctx->n_fused_dots;
     return KNP_OK;
 }
 
