@@ -313,6 +313,26 @@ int knp_gmres_prepare(knp_ctx* ctx, const double* b);
  * on one GPU n_dof_local == n_dof_owned and nothing is written. */
 int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, double atol, int32_t max_it,
                     int32_t restart, int32_t* its, double* rnorm, int32_t* reason);
+/* Flexible GMRES(restart): what the reference gets from PETSc with ksp_type fgmres, or gmres with norm_type unpreconditioned
+ * (right preconditioning), both passed through from the YAML (KNPEMIx_solver.py:80-87, 212, 279).  Classical Gram-Schmidt; per
+ * iteration z_j = B v_j is kept in a second basis Z (so B may change between applications), w = A z_j, and the cycle ends with
+ * x += Z y.  Same arguments, limits, divergence test (1e5 ||b||) and reason codes as knp_gmres_solve, but
+ *   norm:  the TRUE residual: stops when ||b - A x||_2 <= max(rtol ||b||_2, atol) (PETSc KSPConvergedDefault, with or without a
+ *          non-zero initial guess); *rnorm is that norm (the Givens estimate of the last iteration).
+ *   gauge: with the null space on (knp_set_nullspace) each cycle's correction Z y is added without its component along the constant
+ *          potential, so the null-space component of x is that of the initial guess -- what knp_gmres_solve leaves too, whose
+ *          Krylov vectors are projected.  B's output is not projected (A ns = 0: w = A z_j does not see it).
+ *   ghosts: as knp_gmres_solve -- on distributed contexts the ghost entries of b, and of the basis vectors passed to the
+ *          preconditioner, are overwritten by halo exchanges; the owned entries of b are never written.
+ * Z costs restart * n_dof_local doubles of device memory, allocated on the first flexible solve (none with KNP_PC_NONE: Z is V).
+ * On one GPU without Dirichlet rows the first stage of each reduction runs inside the SpMV (cycles up to 8 vectors; KNP_SPMV_DOTS=0
+ * turns it off), and the restart residual b - A x comes with its norm from the same launch.
+ * knp_fgmres_prepare: optional, the counterpart of knp_gmres_prepare -- ||b|| of the next knp_fgmres_solve(ctx, b, ...) on a side
+ * stream now (b complete and not modified until the solve), overlapping whatever the caller enqueues next.  One GPU only; a no-op
+ * on distributed contexts, whose solve computes it in line. */
+int knp_fgmres_prepare(knp_ctx* ctx, const double* b);
+int knp_fgmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, double atol, int32_t max_it,
+                     int32_t restart, int32_t* its, double* rnorm, int32_t* reason);
 
 /* ---- state transfer ---- */
 int knp_pack(knp_ctx* ctx, const knp_fields_out* fields, double* x);
@@ -343,7 +363,8 @@ enum { KNP_ST_BNORM = 0 /* ||B b|| of the last solve */, KNP_ST_ALLREDUCE = 1 /*
        KNP_ST_NORM_FALLBACK = 5 /* GMRES iterations whose norm needed a second reduction (cancellation guard) */,
        KNP_ST_BLOCKED = 6 /* bit h set: the fused cycle of hierarchy h runs on node-blocked operators */,
        KNP_ST_FUSED_LEVELS = 7 /* levels >= 1 that run in fused form inside the level-by-level cycle, all hierarchies */,
-       KNP_ST_FUSED_DOTS = 8 /* reductions whose first stage ran in the preconditioner's last leg (KNP_FUSED_DOTS) */, KNP_ST_COUNT = 9 };
+       KNP_ST_FUSED_DOTS = 8 /* reductions whose first stage ran in the preconditioner's last leg (KNP_FUSED_DOTS) */,
+       KNP_ST_SPMV_DOTS = 9 /* reductions whose first stage ran in the SpMV on A (knp_fgmres_solve, KNP_SPMV_DOTS) */, KNP_ST_COUNT = 10 };
 int knp_get_stats(const knp_ctx* ctx, double* out /* host [KNP_ST_COUNT] */);
 /* bytes the kernels of one application must move, from the sizes of the arrays they read and write (per-class roofline): [0] SpMV on A,
  * [1] one preconditioner application, [2] matrix assembly of one step, [3] right-hand side assembly, [4] one owned vector */

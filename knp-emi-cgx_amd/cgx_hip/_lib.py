@@ -111,6 +111,8 @@ SIGNATURES = {
     "knp_p2p_test_halo": (C.c_int, [vp, C.c_int32, vp, C.c_int32]),
     "knp_p2p_test_allreduce": (C.c_int, [vp, C.c_int32, vp, C.c_int32]),
     "knp_gmres_solve": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_int32, C.c_int32, i32p, f64p, i32p]),
+    "knp_fgmres_prepare": (C.c_int, [vp, vp]),
+    "knp_fgmres_solve": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_int32, C.c_int32, i32p, f64p, i32p]),
     "knp_pack": (C.c_int, [vp, C.POINTER(FieldsOut), vp]),
     "knp_unpack": (C.c_int, [vp, vp, C.POINTER(FieldsOut)]),
     "knp_hh_update": (C.c_int, [vp, vp, vp, vp, vp, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32]),

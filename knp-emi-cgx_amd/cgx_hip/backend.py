@@ -496,6 +496,20 @@ class Backend:
                                             C.byref(rn), C.byref(reason)))
         return its.value, rn.value, reason.value
 
+    def fgmres_prepare(self):
+        """Start ||b|| of the next flexible solve on the library's side stream (b must be final); overlaps the matrix assembly."""
+        self.check(self.lib.knp_fgmres_prepare(self.ctx, C.c_void_p(self.b.data_ptr())))
+
+    def fgmres(self, rtol, atol=1e-50, max_it=5000, restart=30):
+        """Flexible GMRES (right preconditioning): stops on the true residual, ||b - A x|| <= max(rtol ||b||, atol)."""
+        its = C.c_int32()
+        rn = C.c_double()
+        reason = C.c_int32()
+        self.check(self.lib.knp_fgmres_solve(self.ctx, C.c_void_p(self.b.data_ptr()), C.c_void_p(self.x.data_ptr()),
+                                             float(rtol), float(atol), int(max_it), int(restart), C.byref(its),
+                                             C.byref(rn), C.byref(reason)))
+        return its.value, rn.value, reason.value
+
     def matrix_max_abs(self) -> float:
         """max |A_ij| over the locally stored entries (device reduction over the pair-major arrays)."""
         out = C.c_double()
@@ -597,11 +611,11 @@ class Backend:
 
     def stats(self):
         """||B b|| of the last solve and the exchange / read-back counters since the last ``profile_reset``."""
-        out = (C.c_double * 9)()   # KNP_ST_COUNT
+        out = (C.c_double * 10)()   # KNP_ST_COUNT
         self.check(self.lib.knp_get_stats(self.ctx, out))
         return {"bnorm": out[0], "allreduces": int(out[1]), "halos": int(out[2]), "readbacks": int(out[3]), "fused": int(out[4]),
                 "norm_fallbacks": int(out[5]), "blocked": int(out[6]), "fused_levels": int(out[7]),
-                "fused_dots": int(out[8])}
+                "fused_dots": int(out[8]), "spmv_dots": int(out[9])}
 
     def traffic_model(self):
         """bytes one application of each kernel class must move (knp_get_traffic_model)"""

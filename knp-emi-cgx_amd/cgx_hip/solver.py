@@ -8,6 +8,10 @@ Mirrors reference src/CGx/KNPEMI/KNPEMIx_solver.py: same constructor, same class
 Linear solver mapping (reference :211-214, 269-280):
   ksp_type gmres           -> knp_gmres_solve: GMRES(30), left preconditioning, classical
                               Gram-Schmidt, preconditioned norm, non-zero initial guess
+  ksp_type fgmres, or gmres with norm_type unpreconditioned
+                           -> knp_fgmres_solve: flexible GMRES(30), right preconditioning, stops on the
+                              true residual ||b - A x|| <= rtol ||b|| (PETSc's only norm for fgmres; its
+                              right-preconditioned gmres gives the same iterates for a fixed preconditioner)
   pc_type  hypre           -> smoothed-aggregation AMG V-cycle on the block-diagonal P (cgx_hip/amg.py
                               + HIP V-cycle), the native stand-in for BoomerAMG
   pc_type  btcc            -> block lower-triangular variant: AMG on the ion blocks of P, then AMG on the
@@ -90,6 +94,7 @@ class SolverKNPEMI:
     amg_agg_distance = "auto"
     amg_agg_distance_phi = "2"
     _b_is_final = False
+    _flexible = False      # knp_fgmres_solve (fgmres, or gmres with norm_type unpreconditioned)
     btcc_coupled_phi = True  # btcc on one GPU: potential hierarchy on the potential block of A (both sides + membrane coupling), not on P's
     amg_setup = "gpu"      # where the hierarchy is built: "gpu" (torch sparse products, cgx_hip/amg_gpu.py) | "host" (SciPy)
 
@@ -108,12 +113,15 @@ class SolverKNPEMI:
         self.out_file_prefix = problem.output_dir
         self.direct_solver = bool(solver_config["direct"])
         self.view_input = solver_config.get("view_ksp", False)
+        norm_set = False
         if "ksp_settings" in solver_config:
             ks = solver_config["ksp_settings"]
             if "ksp_type" in ks: self.ksp_type = ks["ksp_type"]
             if "pc_type" in ks: self.pc_type = ks["pc_type"]
             if "ksp_rtol" in ks: self.ksp_rtol = float(ks["ksp_rtol"])
-            if "norm_type" in ks: self.norm_type = ks["norm_type"]
+            if "norm_type" in ks:
+                self.norm_type = ks["norm_type"]
+                norm_set = True
             if "strong_threshold" in ks: self.strong_threshold = float(ks["strong_threshold"])
             if "reassemble_P" in ks: self.reassemble_P = bool(ks["reassemble_P"])
             if "non_zero_init_guess" in ks: self.nonzero_init_guess = bool(ks["non_zero_init_guess"])
@@ -123,12 +131,18 @@ class SolverKNPEMI:
             for k in ("amg_theta", "amg_cheby_degree", "amg_pre", "amg_post", "amg_coarse_size", "amg_replicate_below", "amg_fp32", "amg_setup", "amg_node_sync", "amg_split_decoupled",
                       "btcc_coupled_phi", "amg_agg_distance", "amg_agg_distance_phi"):
                 if k in ks: setattr(self, k, type(getattr(self, k))(ks[k]))
-        if self.ksp_type != "gmres":
-            raise NotImplementedError(f"ksp_type '{self.ksp_type}': only 'gmres' is implemented natively.")
+        if self.ksp_type not in ("gmres", "fgmres"):
+            raise NotImplementedError(f"ksp_type '{self.ksp_type}': only 'gmres' and 'fgmres' are implemented natively.")
         if self.pc_type not in ("hypre", "amg", "btcc", "bjacobi", "vbjacobi", "none"):
             raise NotImplementedError(f"pc_type '{self.pc_type}' has no native counterpart (hypre|amg|btcc|bjacobi|vbjacobi|none).")
-        if self.norm_type != "preconditioned":
-            raise NotImplementedError("only norm_type 'preconditioned' is implemented (reference default).")
+        if self.norm_type not in ("preconditioned", "unpreconditioned"):
+            raise NotImplementedError("only norm_type 'preconditioned' (reference default) and 'unpreconditioned' are implemented.")
+        if self.ksp_type == "fgmres" and (self.norm_type != "unpreconditioned" or not norm_set):
+            # PETSc: FGMRES supports right preconditioning with the unpreconditioned norm only (the reference always sets ksp_norm_type)
+            raise ValueError("ksp_type 'fgmres' needs norm_type 'unpreconditioned' (FGMRES supports only right preconditioning).")
+        # flexible GMRES: fgmres, or gmres with the unpreconditioned norm (PETSc then preconditions from the right); the emulated direct
+        # solve keeps its left-preconditioned GMRES
+        self._flexible = not self.direct_solver and self.norm_type == "unpreconditioned"
         if self.save_mat:
             self.time_steps = 1
         self.ksp = _KSPInfo()
@@ -161,7 +175,10 @@ class SolverKNPEMI:
             be.b += torch.as_tensor(extra, dtype=torch.float64, device=be.device)
         be.apply_dirichlet_rhs()
         if self._b_is_final:
-            be.gmres_prepare()
+            if self._flexible:
+                be.fgmres_prepare()
+            else:
+                be.gmres_prepare()
         if not async_matrix:
             be.assemble_matrix()
 
@@ -485,7 +502,8 @@ class SolverKNPEMI:
             np.save(self.out_file_prefix + "Amat", np.c_[A.row, A.col, A.data])
             return False
 
-        its, rnorm, reason = be.gmres(self._rtol, 1e-50, self.ksp_max_it, self.gmres_restart)
+        solve = be.fgmres if self._flexible else be.gmres     # rnorm: true residual norm (flexible) or the preconditioned one
+        its, rnorm, reason = solve(self._rtol, 1e-50, self.ksp_max_it, self.gmres_restart)
         self.ksp.its, self.ksp.rnorm, self.ksp.reason = its, rnorm, reason
         self.tot_its += its
         if self.direct_solver and not p.dirichlet_bcs and not p.pin_ecs_potential:
@@ -562,8 +580,12 @@ class SolverKNPEMI:
         """``--view 1`` / ``view_ksp``: what PETSc's -ksp_view reports for the reference (KNPEMIx_solver.py:285-288), for this solver."""
         pr = self.print
         be = self.backend
-        pr("KSP Object: type gmres (native), restart", self.gmres_restart, ", classical Gram-Schmidt, left preconditioning, "
-           "preconditioned-residual norm, one reduction per iteration")
+        if self._flexible:
+            pr(f"KSP Object: type {self.ksp_type} (native flexible GMRES), restart", self.gmres_restart, ", classical Gram-Schmidt, "
+               "right preconditioning, unpreconditioned (true) residual norm, one reduction per iteration")
+        else:
+            pr("KSP Object: type gmres (native), restart", self.gmres_restart, ", classical Gram-Schmidt, left preconditioning, "
+               "preconditioned-residual norm, one reduction per iteration")
         pr(f"  tolerances: relative={self._rtol:g}, absolute=1e-50, divergence=1e5, maximum iterations={self.ksp_max_it}")
         pr("  initial guess nonzero:", bool(self.nonzero_init_guess or self.direct_solver))
         st = be.stats()
@@ -596,6 +618,8 @@ class SolverKNPEMI:
             pr("Solver type: [" + self.ksp_type + "+" + self.pc_type + "]")
             pr(f"Tolerance: {self.ksp_rtol:.2e}")
             pr(f"Norm type: {self.norm_type}")
+            pr("Krylov method: " + ("flexible GMRES, right preconditioning, stops on ||b - Ax|| <= rtol ||b||" if self._flexible else
+                                    "GMRES, left preconditioning, stops on ||B(b - Ax)|| <= rtol ||B b||"))
             pr(f"None-zero initial guess: {self.nonzero_init_guess}")
             if self.use_P_mat: pr("Preconditioner matrix P enabled.")
             if self.use_block_Jacobi: pr("Using block-Jacobi preconditioner form.")

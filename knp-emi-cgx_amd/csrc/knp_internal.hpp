@@ -271,6 +271,7 @@ struct knp_ctx {
     // preconditioner
     int pc_kind = KNP_PC_NONE;
     int fused_dots = 1;       // first reduction stage in the cycle's last leg (KNP_FUSED_DOTS=0: off)
+    int spmv_dots = 1;        // flexible GMRES: first reduction stage in the SpMV on A (KNP_SPMV_DOTS=0: off)
     double* d_vbj = nullptr;  // [n_nodes_owned*16] compact vertex blocks
     KnpAmgHier hier[KNP_MAX_HIER];   // 0: all fields (block-Jacobi form) or ion fields; 1: potential
     int amg_fp32 = 0;                // store the preconditioner's operators in fp32 (vectors and A stay fp64)
@@ -287,6 +288,8 @@ struct knp_ctx {
     int gm_restart = 0;
     double* d_V = nullptr;       // [(restart+1)*n_dof_local]
     double *d_w = nullptr, *d_t = nullptr;  // [n_dof_local]
+    double* d_Z = nullptr;       // flexible GMRES: the preconditioned basis Z_j = B V_j [restart * n_dof_local], on the first flexible solve
+    int z_cap = 0;               // columns of d_Z
     double* d_partial = nullptr; // reduction scratch
     double* d_red = nullptr;     // [64] reduced values
     double* h_red = nullptr;     // pinned host mirror
@@ -332,6 +335,7 @@ struct knp_ctx {
     hipStream_t stream2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     const double* prep_b = nullptr;
+    const double* fprep_b = nullptr;   // ||b|| of the next knp_fgmres_solve is being computed on the side stream (knp_fgmres_prepare)
     int prep_fused = 0;   // the side-stream ||B b|| used the one-reduction projected norm (flag in slot 61)
     // Concurrent form (one GPU, fused cycle, null space on): the side-stream cycle works on its OWN vectors, partial sums and
     // reduction slots, so it may still be running while the solve computes its first preconditioned residual on the main
@@ -348,6 +352,7 @@ struct knp_ctx {
     double last_bnorm = 0.0;
     int64_t n_allreduce = 0, n_halo = 0, n_readback = 0;
     int64_t n_fused_dots = 0;   // reductions whose first stage ran in the cycle's last leg (KNP_FUSED_DOTS)
+    int64_t n_spmv_dots = 0;    // reductions whose first stage ran in the SpMV on A (KNP_SPMV_DOTS, flexible GMRES)
     // step timers (knp_timer_mark / knp_timer_read): timing events recorded on the main stream, read back in one go
     std::vector<hipEvent_t> tm_events;
     size_t tm_used = 0;

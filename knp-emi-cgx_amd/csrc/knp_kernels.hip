@@ -70,6 +70,8 @@ static void side_discard(knp_ctx* ctx);
 static DevParams make_params(const knp_ctx* ctx);
 static int64_t phi_block_nnz(const knp_ctx* ctx);
 static int join_asm(knp_ctx* ctx);
+static bool fin_ok(const knp_ctx* ctx);
+static hipEvent_t prof_event(knp_ctx* ctx);
 static void free_hier(KnpAmgHier& H);
 static inline int nblocks(int64_t n, int per = NT) { return (int)std::max<int64_t>(1, (n + per - 1) / per); }
 
@@ -1647,6 +1649,174 @@ static bool launch_blevel_up_dots(knp_ctx* ctx, hipStream_t st, const KnpBlocked
     return true;
 }
 
+// ---- the SpMV on A with the first stage of a flexible-GMRES reduction in its epilogue (KNP_SPMV_DOTS) ---------------------------------
+// w = A z (MODE 0) or w = b - A x (MODE 1) as k_spmv_node<G, MODE, MF, U> on the same grid, plus the partial sums V_0.w .. V_{m-1}.w
+// and w.w of each block in rows of SPMV_WIDE (partial[row * SPMV_WIDE + blk], the layout k_reduce_fin takes with that stride).  The
+// vector being orthogonalised in FGMRES is w = A z_j itself, so the fold goes into the SpMV (the preconditioner's last leg produces
+// z_j, which is not reduced).  Lane f < 4 of a node group finishes unknown f: it loads its entries of V_0 .. V_{GV-1} (and of b)
+// right behind the gathers, so that their latency hides under the butterfly; nothing extra is live during the pair loop.
+static constexpr int SPMV_WIDE = 8192;   // (BU_MAX_M + 1) rows of SPMV_WIDE fit the RED_SLOTS x RED_BLOCKS buffer
+static_assert((BU_MAX_M + 1) * SPMV_WIDE <= RED_SLOTS * RED_BLOCKS, "partial-sum buffer");
+template <int G, int MODE, bool MF, int U, int GV>
+__global__ void __launch_bounds__(NT)
+k_spmv_node_dots(int n_list, const int32_t* __restrict__ pair_ptr, const int32_t* __restrict__ pair_col,
+                 const double* __restrict__ ac, const double2* __restrict__ mk, AcCoef coef_i, AcCoef coef_e,
+                 const double* __restrict__ at, const int32_t* __restrict__ node_gv,
+                 const uint8_t* __restrict__ node_side, const int32_t* __restrict__ gptr, const int32_t* __restrict__ gx_i,
+                 const int32_t* __restrict__ gx_e, const double* __restrict__ ax,
+                 const double* __restrict__ x, const double* __restrict__ b, double* __restrict__ y,
+                 int m, int64_t ldv, const double* __restrict__ V, double* __restrict__ partial) {
+    constexpr int MAX_NW = NT / 64;
+    __shared__ double sm[(BU_MAX_M + 1) * MAX_NW];   // sm[v * MAX_NW + wave]: V_0.w .. V_{m-1}.w, w.w
+    const int i = (blockIdx.x * NT + threadIdx.x) / G;
+    const int lane = threadIdx.x & (G - 1);
+    const int wave = threadIdx.x >> 6, wl = threadIdx.x & 63;
+    const bool fin = i < n_list && lane < 4;
+    double y0 = 0.0, y1 = 0.0, y2 = 0.0, y3 = 0.0;
+    double vv[GV], bf = 0.0;
+    const int node = i < n_list ? i : 0;
+    if (i < n_list) {
+        const int p0 = pair_ptr[node];
+        const int p1 = pair_ptr[node + 1];
+        const AcCoef C = (MF && node_side[node]) ? coef_e : coef_i;
+        for (int pb = p0 + lane; pb < p1; pb += U * G) {   // (the pair loop of k_spmv_node)
+            int nb[U];
+            double2 xa[U], xb[U], mv[U], t0[U], t1[U], c0[U], c1[U], c2[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) nb[u] = pair_col[min(pb + u * G, p1 - 1)];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const size_t p = (size_t)min(pb + u * G, p1 - 1);
+                if (MF) {
+                    mv[u] = mk[p];
+                } else {
+                    c0[u] = *reinterpret_cast<const double2*>(ac + 6 * p);
+                    c1[u] = *reinterpret_cast<const double2*>(ac + 6 * p + 2);
+                    c2[u] = *reinterpret_cast<const double2*>(ac + 6 * p + 4);
+                }
+                t0[u] = *reinterpret_cast<const double2*>(at + 4 * p);
+                t1[u] = *reinterpret_cast<const double2*>(at + 4 * p + 2);
+                xa[u] = *reinterpret_cast<const double2*>(x + 4 * (size_t)nb[u]);
+                xb[u] = *reinterpret_cast<const double2*>(x + 4 * (size_t)nb[u] + 2);
+            }
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (u > 0 && pb + u * G >= p1) break;
+                if (MF) ac_entries(C, mv[u].x, mv[u].y, c0[u], c1[u], c2[u]);
+                y0 += c0[u].x * xa[u].x + t0[u].x * xb[u].y;
+                y1 += c0[u].y * xa[u].y + t0[u].y * xb[u].y;
+                y2 += c1[u].x * xb[u].x + t1[u].x * xb[u].y;
+                y3 += c1[u].y * xa[u].x + c2[u].x * xa[u].y + c2[u].y * xb[u].x + t1[u].y * xb[u].y;
+            }
+        }
+        const int A = node_gv[node];
+        if (A >= 0) {
+            const int sd = node_side[node];
+            const int32_t* __restrict__ gx = sd ? gx_e : gx_i;
+            const int s1 = gptr[A + 1];
+            for (int s = gptr[A] + lane; s < s1; s += G) {
+                const double xv = x[4 * (size_t)gx[s] + 3];
+                const double2 v0 = *reinterpret_cast<const double2*>(ax + 8 * (size_t)s + 4 * sd);
+                const double2 v1 = *reinterpret_cast<const double2*>(ax + 8 * (size_t)s + 4 * sd + 2);
+                y0 += v0.x * xv;
+                y1 += v0.y * xv;
+                y2 += v1.x * xv;
+                y3 += v1.y * xv;
+            }
+        }
+    }
+    // this lane's entries of V_0 .. V_{m-1} (and of b): in flight during the butterfly
+#pragma unroll
+    for (int g = 0; g < GV; ++g) vv[g] = (g < m && fin) ? V[(int64_t)g * ldv + 4 * (size_t)node + lane] : 0.0;
+    if (MODE && fin) bf = b[4 * (size_t)node + lane];
+#pragma unroll
+    for (int o = G >> 1; o > 0; o >>= 1) {
+        y0 += __shfl_xor(y0, o, G);
+        y1 += __shfl_xor(y1, o, G);
+        y2 += __shfl_xor(y2, o, G);
+        y3 += __shfl_xor(y3, o, G);
+    }
+    if (lane == 0 && i < n_list) {   // (the stores of k_spmv_node)
+        double2 o0, o1;
+        if (MODE) {
+            const double2 b0 = *reinterpret_cast<const double2*>(b + 4 * (size_t)node);
+            const double2 b1 = *reinterpret_cast<const double2*>(b + 4 * (size_t)node + 2);
+            o0 = make_double2(b0.x - y0, b0.y - y1);
+            o1 = make_double2(b1.x - y2, b1.y - y3);
+        } else {
+            o0 = make_double2(y0, y1);
+            o1 = make_double2(y2, y3);
+        }
+        *reinterpret_cast<double2*>(y + 4 * (size_t)node) = o0;
+        *reinterpret_cast<double2*>(y + 4 * (size_t)node + 2) = o1;
+    }
+    double wf = 0.0;   // entry `lane` of the node's output (the same value lane 0 stores)
+    if (fin) {
+        const double yf = lane == 0 ? y0 : lane == 1 ? y1 : lane == 2 ? y2 : y3;
+        wf = MODE ? bf - yf : yf;
+    }
+#pragma unroll
+    for (int g = 0; g < GV; ++g) {
+        if (g >= m) break;   // (uniform)
+        const double t = wave_sum(vv[g] * wf);
+        if (wl == 0) sm[g * MAX_NW + wave] = t;
+    }
+    {
+        const double t = wave_sum(wf * wf);
+        if (wl == 0) sm[m * MAX_NW + wave] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x <= m) {   // block sums: thread v adds value v of the waves in wave order
+        double t = 0.0;
+#pragma unroll
+        for (int w = 0; w < MAX_NW; ++w) t += sm[threadIdx.x * MAX_NW + w];
+        partial[(size_t)threadIdx.x * SPMV_WIDE + blockIdx.x] = t;
+    }
+}
+// w = A z (residual: w = b - A x) and the first stage of the reduction {V_0.w .. V_{m-1}.w, w.w} in one launch; false when it cannot
+// be taken here (several GPUs, Dirichlet rows, m > BU_MAX_M, more than SPMV_WIDE blocks): the caller then runs spmv_A + k_multi_dot.
+// *nb_out: partial blocks written, in rows of SPMV_WIDE.
+static bool launch_spmv_dots(knp_ctx* ctx, const double* x, const double* b, double* y, int m, int64_t ldv, const double* V, int* nb_out) {
+    const int n_list = ctx->g.n_nodes_owned;
+    const int G = ctx->spmv_group;
+    if (!ctx->spmv_dots || !fin_ok(ctx) || ctx->halo || ctx->p2p || ctx->n_bc > 0 || ctx->d_pair_MK == nullptr || n_list <= 0 || m < 0 ||
+        m > BU_MAX_M || (G != 4 && G != 8 && G != 16 && G != 32))
+        return false;
+    const int nbd = nblocks((int64_t)n_list * G);
+    if (nbd > SPMV_WIDE) return false;
+    if (join_asm(ctx) != KNP_OK) return false;
+    static const int unroll = getenv("KNP_SPMV_UNROLL") ? atoi(getenv("KNP_SPMV_UNROLL")) : 2;
+    const DevParams P = make_params(ctx);
+    const AcCoef ci = ac_coef(P, 0), ce = ac_coef(P, 1);
+    hipEvent_t ea = nullptr, eb = nullptr;
+    if (ctx->prof_on & 1) {
+        ea = prof_event(ctx);
+        eb = prof_event(ctx);
+        if (!ea || !eb) ea = eb = nullptr;
+    }
+#define KNP_SD4(GG, MO, UU, GVV)                                                                                                         \
+    hipExtLaunchKernelGGL((k_spmv_node_dots<GG, MO, true, UU, GVV>), dim3(nbd), dim3(NT), 0, ctx->stream, ea, eb, 0, n_list, ctx->d_pair_ptr, \
+                          ctx->d_pair_col, ctx->d_ac, ctx->d_pair_MK, ci, ce, ctx->d_at, ctx->d_node_gv, ctx->d_node_side, ctx->d_gptr, ctx->d_gx_i, \
+                          ctx->d_gx_e, ctx->d_ax, x, b, y, m, ldv, V, ctx->d_partial)
+#define KNP_SD3(GG, MO, UU) do { if (m <= 3) KNP_SD4(GG, MO, UU, 3); else KNP_SD4(GG, MO, UU, 8); } while (0)
+#define KNP_SD2(GG, MO) do { if (unroll >= 2) KNP_SD3(GG, MO, 2); else KNP_SD3(GG, MO, 1); } while (0)
+#define KNP_SD(GG) do { if (b) KNP_SD2(GG, 1); else KNP_SD2(GG, 0); } while (0)
+    switch (G) {
+        case 4: KNP_SD(4); break;
+        case 8: KNP_SD(8); break;
+        case 16: KNP_SD(16); break;
+        default: KNP_SD(32); break;
+    }
+#undef KNP_SD
+#undef KNP_SD2
+#undef KNP_SD3
+#undef KNP_SD4
+    if (ea && eb) ctx->prof_recs.push_back({ea, eb, 0});
+    ++ctx->n_spmv_dots;
+    *nb_out = nbd;
+    return true;
+}
+
 // setup helpers of the fused cycle
 //   At = c A Dinv on the pattern of a CSR level operator (levels >= 1 in fused form, see amg_vcycle)
 template <typename VI, typename VO>
@@ -1789,6 +1959,7 @@ __device__ __forceinline__ void proj_norm_body(double s, double ww, double* __re
 // single-block kernel instead of k_reduce_partials + k_givens (or + k_proj_norm) -- one launch at the ~4.5 us floor less per GMRES
 // iteration and per norm.  One wave per row, 16 partial sums per lane, fixed order: deterministic.
 //   mode 1: Givens step of iteration j on red[slot0 .. slot0 + nred)      mode 2: gauge-projected norm from {s, w.w}
+//   mode 3: the plain sums red[slot0 .. slot0 + nred), also to mirror[slot0 ..] (the true-residual norm of the flexible solve)
 // s_red[row] = sum_b partial[row * stride + b] for row < nred, b < nb (followed by a barrier): one wave per row, 16 partial sums
 // per lane and chunk of 1024, fixed order -- the same values in every block that calls it
 __device__ __forceinline__ void reduce_partial_rows(int nb, int nred, const double* __restrict__ partial, int stride, double* s_red) {
@@ -1818,8 +1989,18 @@ k_reduce_fin(int mode, int nb, int nred, const double* __restrict__ partial, dou
     reduce_partial_rows(nb, nred, partial, stride, s_red);
     if (threadIdx.x < nred) red[slot0 + threadIdx.x] = s_red[threadIdx.x];
     if (threadIdx.x == 0) {
-        if (mode == 1) givens_body(L, j, has_ns, inv_cnt, s_red, -1, gm, mirror, seq, seq_val);
-        else proj_norm_body(s_red[0], s_red[1], red, slot_out, inv_cnt, cancel, mirror, seq, seq_val);
+        if (mode == 1) {
+            givens_body(L, j, has_ns, inv_cnt, s_red, -1, gm, mirror, seq, seq_val);
+        } else if (mode == 3) {
+            if (mirror)
+                for (int r = 0; r < nred; ++r) mirror[slot0 + r] = s_red[r];
+            if (seq) {
+                __threadfence_system();
+                *seq = seq_val;
+            }
+        } else {
+            proj_norm_body(s_red[0], s_red[1], red, slot_out, inv_cnt, cancel, mirror, seq, seq_val);
+        }
     }
 }
 static bool fin_ok(const knp_ctx* ctx);
@@ -2001,6 +2182,46 @@ __global__ void __launch_bounds__(NT) k_lincomb_solve(GmLayout L, int jd, double
         for (int i = 0; i < jd; ++i) xe += sy[i] * V[(int64_t)i * ldv + e];
         x[e] = xe;
     }
+}
+
+// flexible GMRES, end of a cycle with the null space on: c = Z y into t and the block's sum of the potential entries of c (partial[blk]),
+// so that the correction can be added without its null-space component.  SOLVE (jd <= 8): every block solves the small triangular
+// system itself, as k_lincomb_solve; otherwise y comes from k_gm_solve_y.
+template <bool SOLVE>
+__global__ void __launch_bounds__(NT) k_zcorr(GmLayout L, int jd, double* __restrict__ gm, int n, int64_t ldv, const double* __restrict__ Z,
+                                              double* __restrict__ t, double* __restrict__ partial) {
+    __shared__ double sH[8 * 8], sg[8], sy[8], sm[NT / 64];
+    if (SOLVE) {
+        if (threadIdx.x < jd * jd) sH[threadIdx.x] = gm[L.H(threadIdx.x % jd, threadIdx.x / jd)];
+        if (threadIdx.x < jd) sg[threadIdx.x] = gm[L.g() + threadIdx.x];
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int i = jd - 1; i >= 0; --i) {
+                double s = sg[i];
+                for (int k = i + 1; k < jd; ++k) s -= sH[i + jd * k] * sy[k];
+                sy[i] = s / sH[i + jd * i];
+            }
+            if (blockIdx.x == 0)
+                for (int i = 0; i < jd; ++i) gm[L.y() + i] = sy[i];
+        }
+        __syncthreads();
+    }
+    const double* __restrict__ y = SOLVE ? sy : gm + L.y();
+    double ps = 0.0;
+    for (int e = blockIdx.x * NT + threadIdx.x; e < n; e += gridDim.x * NT) {
+        double c = 0.0;
+        for (int i = 0; i < jd; ++i) c += y[i] * Z[(int64_t)i * ldv + e];
+        t[e] = c;
+        if ((e & 3) == 3) ps += c;
+    }
+    ps = block_sum(ps, sm);
+    if (threadIdx.x == 0) partial[blockIdx.x] = ps;
+}
+// x += t - ns (ns.t): the correction without its null-space component, mean = *phi_sum * inv_count
+__global__ void __launch_bounds__(NT) k_axpy_proj(int n, const double* __restrict__ t, const double* __restrict__ phi_sum, double inv_count,
+                                                  double* __restrict__ x) {
+    const double mean = (*phi_sum) * inv_count;
+    for (int e = blockIdx.x * NT + threadIdx.x; e < n; e += gridDim.x * NT) x[e] += (e & 3) == 3 ? t[e] - mean : t[e];
 }
 
 __global__ void __launch_bounds__(NT) k_axpy(int n, double a, const double* __restrict__ x, double* __restrict__ y) {
@@ -2881,7 +3102,7 @@ int knp_destroy(knp_ctx* ctx) {
     dev_free(ctx->d_partial); dev_free(ctx->d_red); dev_free(ctx->d_y); dev_free(ctx->d_vbj); dev_free(ctx->d_gm);
     if (ctx->h_red) (void)hipHostFree(ctx->h_red);
     if (ctx->h_seq) (void)hipHostFree((void*)ctx->h_seq);
-    dev_free(ctx->d_V); dev_free(ctx->d_w); dev_free(ctx->d_t);
+    dev_free(ctx->d_V); dev_free(ctx->d_Z); dev_free(ctx->d_w); dev_free(ctx->d_t);
     for (auto& p : ctx->progs) { dev_free(p.d_code); dev_free(p.d_consts); if (p.h_consts) (void)hipHostFree(p.h_consts); }
     dev_free(ctx->d_prog_code); dev_free(ctx->d_prog_consts); dev_free(ctx->d_prog_len); dev_free(ctx->d_prog_nconsts);
     for (int h = 0; h < KNP_MAX_HIER; ++h) free_hier(ctx->hier[h]);
@@ -4424,6 +4645,7 @@ int knp_pc_setup(knp_ctx* ctx, int32_t kind) {
     }
     ctx->pc_kind = kind;
     ctx->fused_dots = !(getenv("KNP_FUSED_DOTS") && atoi(getenv("KNP_FUSED_DOTS")) == 0);   // read at every knp_pc_setup, like KNP_FUSED
+    ctx->spmv_dots = !(getenv("KNP_SPMV_DOTS") && atoi(getenv("KNP_SPMV_DOTS")) == 0);
     for (int h = 0; h < KNP_MAX_HIER; ++h) ctx->hier[h].fused = 0;
     if (kind == KNP_PC_AMG) ctx->hier[0].fused = fused_eligible(ctx, ctx->hier[0]) ? 1 : 0;
     if (kind == KNP_PC_AMG_BT || kind == KNP_PC_AMG_LT) {   // both or none: the potential hierarchy then works on compact vectors
@@ -4635,6 +4857,10 @@ static void side_discard(knp_ctx* ctx) {   // any call that could touch what the
         if (!ctx->prep_deferred) (void)hipEventSynchronize(ctx->ev_join);   // deferred: nothing was enqueued yet
         ctx->prep_b = nullptr;
         ctx->prep_deferred = false;
+    }
+    if (ctx->fprep_b) {
+        (void)hipEventSynchronize(ctx->ev_join);
+        ctx->fprep_b = nullptr;
     }
 }
 
@@ -5040,6 +5266,231 @@ int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doubl
     return KNP_OK;
 }
 
+// ---- flexible GMRES(restart), right preconditioning, true-residual norm (KSPFGMRES; KSPGMRES with norm_type unpreconditioned) --------
+// Per iteration: z_j = B v_j kept in a second basis Z (B may change between applications), w = A z_j, classical Gram-Schmidt of w
+// against V with ONE reduction {V_i.w, w.w} whose first stage runs in the SpMV itself on one GPU (k_spmv_node_dots), Givens step and
+// v_{j+1} as in knp_gmres_solve.  Cycle end: x += Z y.  The residual estimate |g_{j+1}| is ||b - A x||_2.
+static constexpr int FB_SLOT = 124;   // ||b||^2 of the flexible solve (knp_fgmres_prepare on the side stream, or in line)
+static int ensure_z(knp_ctx* ctx, int restart) {
+    if (ctx->d_Z && ctx->z_cap >= restart) return KNP_OK;
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    dev_free(ctx->d_Z);
+    const size_t bytes = (size_t)restart * std::max(ctx->n_dof_local, 1) * sizeof(double);
+    HIPCHK(hipMalloc((void**)&ctx->d_Z, bytes));
+    HIPCHK(hipMemset(ctx->d_Z, 0, bytes));
+    ctx->z_cap = restart;
+    return KNP_OK;
+}
+
+int knp_fgmres_prepare(knp_ctx* ctx, const double* b) {
+    CHECK_CTX(ctx);
+    if (!b) return KNP_E_ARG;
+    side_discard(ctx);
+    // one GPU only: on distributed contexts ||b|| needs an all-reduce, which the solve does in line
+    if (getenv("KNP_NO_PREPARE") || (ctx->prof_on & ~1) || ctx->halo || ctx->allreduce || ctx->level_comm || ctx->p2p) return KNP_OK;
+    if (!ctx->stream2) {
+        HIPCHK(hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
+        HIPCHK(hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+    }
+    if (!ctx->d_partial_s) {
+        HIPCHK(hipMalloc((void**)&ctx->d_partial_s, (size_t)RED_SLOTS * RED_BLOCKS * sizeof(double)));
+        HIPCHK(hipMemset(ctx->d_partial_s, 0, (size_t)RED_SLOTS * RED_BLOCKS * sizeof(double)));
+    }
+    const int nb = ctx->n_red_blocks;
+    HIPCHK(hipEventRecord(ctx->ev_fork, ctx->stream));
+    HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
+    hipLaunchKernelGGL(k_dot, dim3(nb), dim3(NT), 0, ctx->stream2, ctx->n_dof_owned, b, b, ctx->d_partial_s);
+    hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(NT), 0, ctx->stream2, nb, ctx->d_partial_s, ctx->d_red, FB_SLOT, ctx->mirror(),
+                       (volatile int64_t*)nullptr, (int64_t)0);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
+    ctx->fprep_b = b;
+    return KNP_OK;
+}
+
+int knp_fgmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, double atol, int32_t max_it, int32_t restart,
+                     int32_t* its, double* rnorm, int32_t* reason) {
+    CHECK_CTX(ctx);
+    if (!b || !x || !its || !rnorm || !reason) return KNP_E_ARG;
+    if (!ctx->have_A) { ctx->err = "matrix not assembled"; return KNP_E_STATE; }
+    constexpr int GM_RES = 100, GM_EXPL = 57, GM_MAX_RESTART = GM_EXPL - 2;   // the slot layout of knp_gmres_solve
+    if (restart < 1 || restart > GM_MAX_RESTART || max_it < 0) {
+        ctx->err = "restart must be in [1," + std::to_string(GM_MAX_RESTART) + "] and max_it >= 0";
+        return KNP_E_ARG;
+    }
+    KCHK(ensure_work(ctx, restart));
+    const bool pc_none = ctx->pc_kind == KNP_PC_NONE;
+    if (!pc_none) KCHK(ensure_z(ctx, restart));   // with no preconditioner Z is V: nothing is allocated or copied
+    prof_collect_ready(ctx);
+    const int n = ctx->n_dof_owned;
+    const int64_t ldv = ctx->n_dof_local;
+    const int nb = ctx->n_red_blocks;
+    hipStream_t st = ctx->stream;
+    int rc;
+    const int64_t cnt = ctx->ns_on ? global_phi_count(ctx, &rc) : 0;
+    if (ctx->ns_on) KCHK(rc);
+    const int m = restart;
+    const GmLayout GL{m};
+    if (ctx->gm_cap < GL.size()) {
+        HIPCHK(hipStreamSynchronize(st));
+        dev_free(ctx->d_gm);
+        HIPCHK(hipMalloc((void**)&ctx->d_gm, (size_t)GL.size() * sizeof(double)));
+        HIPCHK(hipMemset(ctx->d_gm, 0, (size_t)GL.size() * sizeof(double)));
+        ctx->gm_cap = GL.size();
+    }
+    double* gm = ctx->d_gm;
+    auto read_state = [&](double& res_out, int& flag_out) -> int {   // as in knp_gmres_solve
+        ++ctx->n_readback;
+        if (ctx->mirror() && ctx->h_seq_dev) {
+            KCHK(read_slots_inner(ctx, GM_RES, 2, ctx->seq_counter));
+            if (ctx->p2p) KCHK(knp_p2p_check(ctx));
+            res_out = ctx->h_red[GM_RES];
+            flag_out = (int)ctx->h_red[GM_RES + 1];
+        } else {
+            double tmp[3];
+            HIPCHK(hipMemcpyAsync(tmp, gm + GL.st(), 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+            HIPCHK(hipStreamSynchronize(st));
+            res_out = tmp[2];
+            flag_out = (int)tmp[1];
+        }
+        return KNP_OK;
+    };
+
+    // ||b|| for the relative tolerance (PETSc's KSPConvergedDefault with the unpreconditioned norm, initial guess zero or not)
+    if (ctx->fprep_b == b) {
+        HIPCHK(hipEventSynchronize(ctx->ev_join));
+        ctx->fprep_b = nullptr;
+        if (!ctx->mirror()) HIPCHK(hipMemcpy(ctx->h_red + FB_SLOT, ctx->d_red + FB_SLOT, sizeof(double), hipMemcpyDeviceToHost));
+    } else {
+        side_discard(ctx);
+        KCHK(dot_to_slot(ctx, b, b, FB_SLOT));
+        KCHK(read_slots(ctx, FB_SLOT, 1, ctx->seq_counter));
+    }
+    const double bnorm = std::sqrt(ctx->h_red[FB_SLOT]);
+    ctx->last_bnorm = bnorm;
+    if (!std::isfinite(bnorm)) { *its = 0; *rnorm = bnorm; *reason = KNP_DIVERGED_NANORINF; return KNP_OK; }
+    const double ttol = std::max(rtol * bnorm, atol);
+    const double dtol = 1e5;
+    int it = 0;
+    double res = 0.0, res0 = -1.0;
+    *reason = 0;
+    const bool ns = ctx->ns_on && cnt > 0;
+    const int vec_blocks = std::min(nblocks(n), 2048);
+    double* Zb = pc_none ? ctx->d_V : ctx->d_Z;
+    while (true) {
+        // r = b - A x and ||r||^2: one launch on one GPU (the residual form of the SpMV with its own norm), else SpMV + dot
+        {
+            int nbd = 0;
+            if (launch_spmv_dots(ctx, x, b, ctx->d_w, 0, ldv, ctx->d_V, &nbd)) {
+                ++ctx->n_allreduce;
+                hipLaunchKernelGGL(k_reduce_fin, dim3(1), dim3(NT), 0, st, 3, nbd, 1, ctx->d_partial, ctx->d_red, 60, GL, 0, 0, 0.0, (double*)nullptr, 0,
+                                   0.0, ctx->mirror(), ctx->mirror() ? ctx->h_seq_dev : nullptr, ++ctx->seq_counter, SPMV_WIDE);
+                HIPCHK(hipGetLastError());
+            } else {
+                KCHK(spmv_A(ctx, x, b, ctx->d_w, true));
+                KCHK(dot_to_slot(ctx, ctx->d_w, ctx->d_w, 60));
+            }
+            KCHK(read_slots(ctx, 60, 1, ctx->seq_counter));
+        }
+        const double beta = std::sqrt(ctx->h_red[60]);
+        res = beta;
+        if (res0 < 0) res0 = beta;
+        if (!std::isfinite(beta)) { *reason = KNP_DIVERGED_NANORINF; break; }
+        if (beta <= ttol) { *reason = (beta <= atol) ? KNP_CONVERGED_ATOL : KNP_CONVERGED_RTOL; break; }
+        if (it >= max_it) { *reason = KNP_DIVERGED_ITS; break; }
+        // v_0 = r / beta and g = (beta, 0, ..., 0) in one pass (k_scale_rsqrt_proj with a zero mean: r is not projected)
+        hipLaunchKernelGGL(k_scale_rsqrt_proj, dim3(vec_blocks), dim3(NT), 0, st, n, ctx->d_w, ctx->d_red + 60, ctx->d_red + 60, 0.0, ctx->d_V,
+                           gm + GL.g(), m);
+        int jd = 0;
+        bool stop = false;
+        for (int j = 0; j < m; ++j) {
+            double* vj = ctx->d_V + (size_t)j * ldv;
+            double* vn = ctx->d_V + (size_t)(j + 1) * ldv;
+            double* zj = Zb + (size_t)j * ldv;
+            // z_j = B v_j, unprojected: A ns = 0, so w = A z_j does not see its gauge part (the correction is projected once per cycle)
+            if (!pc_none) KCHK(pc_apply_proj(ctx, vj, zj, 0));
+            int flag = 0;
+            {
+                int nbd = 0;
+                const bool folded = j + 1 <= BU_MAX_M && launch_spmv_dots(ctx, zj, nullptr, ctx->d_w, j + 1, ldv, ctx->d_V, &nbd);
+                if (!folded) KCHK(spmv_A(ctx, zj, nullptr, ctx->d_w, false));
+                ProfScope ps(ctx, 1);
+                for (int i0 = 0; i0 <= j && !folded; i0 += 8) {   // owned rows; the first launch also takes w.w
+                    if (i0 == 0)
+                        hipLaunchKernelGGL((k_multi_dot<8, false, true>), dim3(nb), dim3(NT), 0, st, n, ldv, i0, j + 1, ctx->d_V, ctx->d_w, ctx->d_partial);
+                    else
+                        hipLaunchKernelGGL((k_multi_dot<8, false, false>), dim3(nb), dim3(NT), 0, st, n, ldv, i0, j + 1, ctx->d_V, ctx->d_w, ctx->d_partial);
+                }
+                const int nred = j + 2;
+                if (fin_ok(ctx)) {
+                    ++ctx->n_allreduce;
+                    hipLaunchKernelGGL(k_reduce_fin, dim3(1), dim3(NT), 0, st, 1, folded ? nbd : nb, nred, ctx->d_partial, ctx->d_red, 0, GL, j, 0, 0.0, gm,
+                                       0, 0.0, ctx->mirror() ? ctx->h_red_dev + GM_RES : nullptr, ctx->mirror() ? ctx->h_seq_dev : nullptr, ++ctx->seq_counter,
+                                       folded ? SPMV_WIDE : RED_BLOCKS);
+                } else {
+                    hipLaunchKernelGGL(k_reduce_partials, dim3(nred), dim3(NT), 0, st, nb, ctx->d_partial, ctx->d_red, 0, (double*)nullptr);
+                    KCHK(allreduce_slots(ctx, 0, nred));
+                    hipLaunchKernelGGL(k_givens, dim3(1), dim3(64), 0, st, GL, j, 0, 0.0, ctx->d_red, -1, gm,
+                                       ctx->mirror() ? ctx->h_red_dev + GM_RES : nullptr, ctx->mirror() ? ctx->h_seq_dev : nullptr, ++ctx->seq_counter);
+                }
+                hipLaunchKernelGGL(k_update_scale, dim3(nb), dim3(NT), 0, st, n, ldv, j + 1, ctx->d_V, ctx->d_red, ctx->d_w, gm + GL.st(), 0.0, vn);
+                HIPCHK(hipGetLastError());
+            }
+            KCHK(read_state(res, flag));
+            if (flag == 1) {   // cancellation: explicit norm of the (unnormalised) vector, second reduction of this iteration
+                ProfScope ps(ctx, 1);
+                ++ctx->n_norm_fallback;
+                hipLaunchKernelGGL(k_dot, dim3(nb), dim3(NT), 0, st, n, vn, vn, ctx->d_partial);
+                hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(NT), 0, st, nb, ctx->d_partial, ctx->d_red, GM_EXPL, (double*)nullptr);
+                KCHK(allreduce_slots(ctx, GM_EXPL, 1));
+                hipLaunchKernelGGL(k_givens, dim3(1), dim3(64), 0, st, GL, j, 0, 0.0, ctx->d_red, GM_EXPL, gm,
+                                   ctx->mirror() ? ctx->h_red_dev + GM_RES : nullptr, ctx->mirror() ? ctx->h_seq_dev : nullptr, ++ctx->seq_counter);
+                hipLaunchKernelGGL(k_scale_inplace_rsqrt, dim3(vec_blocks), dim3(NT), 0, st, n, gm + GL.st(), vn);
+                HIPCHK(hipGetLastError());
+                KCHK(read_state(res, flag));
+            }
+            if (flag != 0 || !std::isfinite(res)) { *reason = KNP_DIVERGED_NANORINF; stop = true; jd = j; break; }
+            ++it;
+            jd = j + 1;
+            if (res <= ttol) { *reason = (res <= atol) ? KNP_CONVERGED_ATOL : KNP_CONVERGED_RTOL; stop = true; break; }
+            if (it >= max_it) { *reason = KNP_DIVERGED_ITS; stop = true; break; }
+            if (res > dtol * (bnorm > 0.0 ? bnorm : res0)) { *reason = KNP_DIVERGED_DTOL; stop = true; break; }
+        }
+        if (jd > 0) {   // x += Z y, without its null-space component when there is one (x keeps the gauge of the initial guess)
+            ProfScope ps(ctx, 1);
+            if (ns) {
+                if (jd <= 8) {
+                    hipLaunchKernelGGL(k_zcorr<true>, dim3(nb), dim3(NT), 0, st, GL, jd, gm, n, ldv, Zb, ctx->d_t, ctx->d_partial);
+                } else {
+                    hipLaunchKernelGGL(k_gm_solve_y, dim3(1), dim3(64), 0, st, GL, jd, gm);
+                    hipLaunchKernelGGL(k_zcorr<false>, dim3(nb), dim3(NT), 0, st, GL, jd, gm, n, ldv, Zb, ctx->d_t, ctx->d_partial);
+                }
+                hipLaunchKernelGGL(k_reduce_partials, dim3(1), dim3(NT), 0, st, nb, ctx->d_partial, ctx->d_red, 62, (double*)nullptr);
+                KCHK(allreduce_slots(ctx, 62, 1));
+                hipLaunchKernelGGL(k_axpy_proj, dim3(vec_blocks), dim3(NT), 0, st, n, ctx->d_t, ctx->d_red + 62, 1.0 / (double)cnt, x);
+            } else if (jd <= 8) {
+                hipLaunchKernelGGL(k_lincomb_solve, dim3(vec_blocks), dim3(NT), 0, st, GL, jd, gm, n, ldv, Zb, x);
+            } else {
+                hipLaunchKernelGGL(k_gm_solve_y, dim3(1), dim3(64), 0, st, GL, jd, gm);
+                hipLaunchKernelGGL(k_lincomb, dim3(vec_blocks), dim3(NT), 0, st, n, ldv, jd, Zb, gm + GL.y(), x);
+            }
+            HIPCHK(hipGetLastError());
+        }
+        if (stop) break;
+    }
+    *its = it;
+    *rnorm = res;
+    KCHK(halo_update(ctx, x));
+    HIPCHK(hipGetLastError());
+    if (ctx->p2p) {
+        HIPCHK(hipStreamSynchronize(st));
+        KCHK(knp_p2p_check(ctx));
+    }
+    if (ctx->comm_rc != KNP_OK) { const int rc2 = ctx->comm_rc; ctx->comm_rc = KNP_OK; return rc2; }
+    return KNP_OK;
+}
+
 // ---- state transfer -------------------------------------------------------------------------
 static int out_ptrs(knp_ctx* ctx, const knp_fields_out* f, OutPtrs& o, bool need_phim) {
     if (!f) { ctx->err = "null fields"; return KNP_E_ARG; }
@@ -5156,6 +5607,7 @@ int knp_profile_reset(knp_ctx* ctx) {
     for (int i = 0; i < KNP_NPROF; ++i) { ctx->prof_ms[i] = 0; ctx->prof_n[i] = 0; }
     ctx->n_allreduce = ctx->n_halo = ctx->n_readback = ctx->n_norm_fallback = 0;
     ctx->n_fused_dots = 0;
+    ctx->n_spmv_dots = 0;
     return KNP_OK;
 }
 // Bytes the kernels of one application must move, from the sizes of the arrays they read and write (the "algorithmic bytes" of the
@@ -5233,6 +5685,7 @@ int knp_get_stats(const knp_ctx* ctx, double* out) {
         for (int l = 1; l < ctx->hier[h].levels; ++l) nlf += ctx->hier[h].lv[l].lfused;
     out[KNP_ST_FUSED_LEVELS] = (double)nlf;
     out[KNP_ST_FUSED_DOTS] = (double)ctx->n_fused_dots;
+    out[KNP_ST_SPMV_DOTS] = (double)ctx->n_spmv_dots;
     return KNP_OK;
 }
 
