@@ -29,6 +29,10 @@
  *   knp_hh_update                    HodgkinHuxley.update_gating_variables
  *                                    (KNPEMIx_ionic_model.py:605-671)
  *   knp_l2_norms                     assemble_scalar(inner(phi,phi)*dx(tag)) (src/CGx/KNPEMI/main.py:70-84)
+ *   knp_diag_set_cell_tags / knp_diag_volume_integrals
+ *        assemble_scalar(k*dx(tag)) per ion and cell tag of print_conservation (KNPEMIx_problem.py:821-840)
+ *   knp_diag_set_facet_tags / knp_diag_set_program / knp_diag_set_program_constants / knp_diag_membrane_integral
+ *        assemble_scalar(stim_ufl_expr*dS(stimulus_tags)) of the stimulus trace (KNPEMIx_solver.py:580-582, 605-607)
  *   knp_set_comm                     the MPI calls hidden in PETSc/DOLFINx (ghost updates
  *                                    KNPEMIx_solver.py:439,459,468; Allreduce inside KSPSolve)
  *
@@ -58,6 +62,7 @@ extern "C" {
 
 #define KNP_MAX_IONS 3
 #define KNP_MAX_AUX 8
+#define KNP_DIAG_MAX_CONSTS 64   /* constants of a diagnostic program (knp_diag_set_program) */
 #define KNP_MAX_PROG_REGS 48
 #define KNP_MAX_AMG_LEVELS 16
 
@@ -340,6 +345,31 @@ int knp_unpack(knp_ctx* ctx, const double* x, const knp_fields_out* fields);
 int knp_hh_update(knp_ctx* ctx, const double* phi_m, double* n, double* m, double* h, int32_t count,
                   double dt, double phi_rest, int32_t rush_larsen, int32_t substeps);
 int knp_l2_norms(knp_ctx* ctx, const double* phi_i, const double* phi_e, double* out /* host [2]: squared, owned cells */);
+/* Per-tag diagnostics.  A tag map lists items sorted by a dense tag index: seg_ptr[t] .. seg_ptr[t+1]-1 are the positions of tag t in
+ * `cells` / `facets`; seg_ptr[0] == 0, non-decreasing; every item at most once.  The maps are uploaded once (synchronous); the
+ * integrals are enqueued on the library's stream, write the caller's device buffer and never wait for the device.  No atomics: the
+ * same inputs give the same bits on every run.  Each rank integrates what it lists; the caller sums over ranks.
+ * knp_diag_set_cell_tags: owned cells only (ids < n_cells_owned).
+ * knp_diag_volume_integrals: out[3t + j] = sum over the cells c of tag t of |c|/(d+1) * sum over the vertices of c of k_j on the
+ *   cell's side (fields->k_i for intracellular cells, k_e for extracellular ones): the exact P1 integral, i.e. assemble_scalar of
+ *   k_j*dx(tag) in print_conservation (KNPEMIx_problem.py:821-840). */
+int knp_diag_set_cell_tags(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr /* host [n_tags+1] */,
+                           const int32_t* cells /* host [seg_ptr[n_tags]] */);
+int knp_diag_volume_integrals(knp_ctx* ctx, const knp_fields* fields, double* out /* device [n_tags*3] */);
+/* knp_diag_set_facet_tags: membrane facets by their index in knp_mesh_desc.gamma; the caller selects them (one owner per facet, e.g.
+ *   the rank owning the facet's first vertex) and may give several membrane tags the same index.
+ * knp_diag_set_program: one bytecode program (the opcodes of knp_set_program, at most KNP_DIAG_MAX_CONSTS constants), kept apart from
+ *   the assembly's program table; knp_diag_set_program_constants replaces its constants on the host (they travel as kernel arguments
+ *   of the next knp_diag_membrane_integral: no copy, no synchronisation).
+ * knp_diag_membrane_integral: out[t] = sum over the facets F of tag t and the quadrature points q of q_w |F| times the sum of the
+ *   program's outputs at q (bytecode interpreter): assemble_scalar(stim_ufl_expr*dS(stimulus_tags)) of the stimulus trace
+ *   (KNPEMIx_solver.py:580-582, 605-607). */
+int knp_diag_set_facet_tags(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr /* host [n_tags+1] */,
+                            const int32_t* facets /* host [seg_ptr[n_tags]] */);
+int knp_diag_set_program(knp_ctx* ctx, int32_t n_instr, const int32_t* code /* host [n_instr*4] */, int32_t n_consts,
+                         const double* consts /* host */);
+int knp_diag_set_program_constants(knp_ctx* ctx, int32_t n_consts, const double* consts /* host */);
+int knp_diag_membrane_integral(knp_ctx* ctx, const knp_fields* fields, double* out /* device [n_tags] */);
 
 /* ---- instrumentation ---- */
 /* elapsed ms and launch count of a kernel class since the last reset (HIP events on the ctx stream).

@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libknpemi_hip.so")
 KNP_MAX_IONS = 3
 KNP_MAX_AUX = 8
 KNP_MAX_PROG_REGS = 48
+KNP_DIAG_MAX_CONSTS = 64
 KNP_SZ_COUNT = 16
 (SZ_N_NODES, SZ_N_NODES_OWNED, SZ_N_DOF_LOCAL, SZ_N_DOF_OWNED, SZ_NNZ, SZ_N_PAIRS, SZ_N_CONTRIB,
  SZ_N_GAMMA_VERTS, SZ_N_GAMMA_PAIRS, SZ_NNZ_P, SZ_N_PHI_OWNED, SZ_NNZ_P_PHI) = range(12)
@@ -117,6 +118,12 @@ SIGNATURES = {
     "knp_unpack": (C.c_int, [vp, vp, C.POINTER(FieldsOut)]),
     "knp_hh_update": (C.c_int, [vp, vp, vp, vp, vp, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32]),
     "knp_l2_norms": (C.c_int, [vp, vp, vp, f64p]),
+    "knp_diag_set_cell_tags": (C.c_int, [vp, C.c_int32, i32p, i32p]),
+    "knp_diag_volume_integrals": (C.c_int, [vp, C.POINTER(Fields), vp]),
+    "knp_diag_set_facet_tags": (C.c_int, [vp, C.c_int32, i32p, i32p]),
+    "knp_diag_set_program": (C.c_int, [vp, C.c_int32, i32p, C.c_int32, f64p]),
+    "knp_diag_set_program_constants": (C.c_int, [vp, C.c_int32, f64p]),
+    "knp_diag_membrane_integral": (C.c_int, [vp, C.POINTER(Fields), vp]),
     "knp_timer_mark": (C.c_int, [vp, C.c_int32]),
     "knp_timer_read": (C.c_int, [vp, C.c_int32, f64p, C.POINTER(C.c_int32)]),
     "knp_timer_pending": (C.c_int, [vp]),

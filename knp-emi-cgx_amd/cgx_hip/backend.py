@@ -522,8 +522,66 @@ class Backend:
         self.check(self.lib.knp_l2_norms(self.ctx, C.c_void_p(p.wh[0][3].data_ptr()), C.c_void_p(p.wh[1][3].data_ptr()), out))
         return p.comm.allreduce_sum(out[0]), p.comm.allreduce_sum(out[1])
 
+    # ---- per-tag diagnostics (csrc/knp_diagnostics.inc) ------------------------------------
+    def budget_layout(self):
+        """cell tags, owned cells sorted by tag, per-tag volumes and areas (cgx_hip/diagnostics.py); the map is uploaded once"""
+        if getattr(self, "_budget", None) is None:
+            from .diagnostics import BudgetLayout
+            lay = BudgetLayout(self.p)
+            self.check(self.lib.knp_diag_set_cell_tags(self.ctx, lay.n_tags, _i32(lay.seg_ptr), _i32(lay.cells) if lay.cells.size else None))
+            self._keep += [lay.seg_ptr, lay.cells]
+            self._budget = lay
+        return self._budget
+
+    def ion_amounts(self, out=None):
+        """This rank's amount of each ion per cell tag, [n_tags, 3] on the device: enqueued, not waited for.  ``out``: a
+        contiguous float64 device tensor of that shape (a row of a preallocated trace), else a new one."""
+        lay = self.budget_layout()
+        if out is None:
+            out = torch.empty((lay.n_tags, 3), dtype=torch.float64, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.float64 and out.numel() == 3 * lay.n_tags
+        f = self.fields()
+        self.check(self.lib.knp_diag_volume_integrals(self.ctx, C.byref(f), C.c_void_p(out.data_ptr())))
+        return out
+
     def total_ion_amounts(self):
-        raise NotImplementedError
+        """int k dx_i + int k dx_e for Na, K, Cl [mol], summed over ranks (print_conservation, KNPEMIx_problem.py:821-827)"""
+        loc = self.ion_amounts().sum(dim=0).cpu().numpy()
+        return np.array([self.p.comm.allreduce_sum(float(v)) for v in loc])
+
+    def set_facet_groups(self, groups):
+        """Membrane facets of this rank (owner of the first vertex) whose membrane tag is in ``groups[t]``, reduced into slot t
+        of ``membrane_integral``; a facet goes to the first group that lists its tag"""
+        from .diagnostics import owned_facets, tag_map
+        p = self.p
+        own = np.nonzero(owned_facets(p))[0]
+        ftags = np.asarray(p.gamma_facet_tags)[own]
+        group_of = np.full(len(own), -1, dtype=np.int64)
+        for t, tags in reversed(list(enumerate(groups))):
+            group_of[np.isin(ftags, list(tags))] = t
+        seg_ptr, items = tag_map(group_of, np.arange(len(groups)))
+        facets = np.ascontiguousarray(own[items], dtype=np.int32)
+        self.check(self.lib.knp_diag_set_facet_tags(self.ctx, len(groups), _i32(seg_ptr), _i32(facets) if facets.size else None))
+        self._keep += [seg_ptr, facets]
+        self.n_facet_groups = len(groups)
+
+    def set_diag_program(self, spec):
+        code = np.ascontiguousarray(spec.code, dtype=np.int32)
+        consts = spec.constants()
+        if consts.shape[0] > _lib.KNP_DIAG_MAX_CONSTS:
+            raise ValueError(f"a diagnostic program takes at most {_lib.KNP_DIAG_MAX_CONSTS} constants")
+        self.check(self.lib.knp_diag_set_program(self.ctx, code.shape[0], _i32(code), consts.shape[0], _f64(consts) if consts.size else None))
+
+    def refresh_diag_constants(self, spec):
+        consts = spec.constants()
+        self.check(self.lib.knp_diag_set_program_constants(self.ctx, consts.shape[0], _f64(consts) if consts.size else None))
+
+    def membrane_integral(self, out):
+        """integral of the diagnostic program over each facet group into the device tensor ``out`` [n_groups] (enqueued)"""
+        assert out.is_contiguous() and out.dtype == torch.float64 and out.numel() == self.n_facet_groups
+        f = self.fields()
+        self.check(self.lib.knp_diag_membrane_integral(self.ctx, C.byref(f), C.c_void_p(out.data_ptr())))
+        return out
 
     # ---- exports (parity hooks) ------------------------------------------------------------
     def csr(self):

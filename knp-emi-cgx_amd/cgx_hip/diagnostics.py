@@ -1,0 +1,97 @@
+"""Per-tag diagnostics of a run: ion amounts, charge, volume and membrane area per cell tag (reference
+KNPEMIx_problem.py:807-843, ``print_conservation``) and the stimulus-current trace (KNPEMIx_solver.py:578-585, 604-610, 855-857).
+
+The tag maps and the time-invariant measures are built here, on the host, once; the integrals of the fields are HIP kernels
+(csrc/knp_diagnostics.inc, ``knp_diag_*``) that run on the library's stream and write device buffers.  Reading a result is the
+only synchronisation, and the time loop never reads one unless the problem prints every step.
+"""
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from . import fem
+
+# valences the reference hard-codes in the charge of print_conservation (KNPEMIx_problem.py:840)
+CHARGE_VALENCES = (1.0, 1.0, -1.0)
+
+
+def tag_map(item_tags, tag_values):
+    """Items (cells or facets) sorted by the dense index of their tag in ``tag_values``: returns ``seg_ptr`` [n_tags + 1] and
+    ``items`` (positions in ``item_tags``), int32.  Items whose tag is not listed are left out; the sort is stable."""
+    tag_values = np.asarray(tag_values, dtype=np.int64)
+    item_tags = np.asarray(item_tags, dtype=np.int64)
+    if len(np.unique(tag_values)) != len(tag_values):
+        raise ValueError("tag values must be distinct")
+    order = np.argsort(tag_values, kind="stable")
+    pos = np.searchsorted(tag_values[order], item_tags)
+    pos = np.minimum(pos, max(len(tag_values) - 1, 0))
+    known = (tag_values[order][pos] == item_tags) if len(tag_values) else np.zeros(len(item_tags), bool)
+    dense = np.where(known, order[pos] if len(tag_values) else 0, -1)
+    sel = np.nonzero(dense >= 0)[0]
+    items = sel[np.argsort(dense[sel], kind="stable")].astype(np.int32)
+    counts = np.bincount(dense[sel], minlength=len(tag_values))
+    seg_ptr = np.zeros(len(tag_values) + 1, dtype=np.int32)
+    np.cumsum(counts, out=seg_ptr[1:])
+    return seg_ptr, items
+
+
+def cell_volumes(coords, cells):
+    d = coords.shape[1]
+    X = coords[cells]
+    return np.abs(np.linalg.det(X[:, 1:, :] - X[:, :1, :])) / math.factorial(d)
+
+
+def owned_facets(problem):
+    """Membrane facets this rank counts: the owner of the facet's first vertex (rule of ``integrate_over_membrane``)."""
+    lm = problem.local_mesh
+    if not len(problem._fv):
+        return np.zeros(0, dtype=bool)
+    return problem._fv[:, 0] < lm.n_vertices_owned
+
+
+class BudgetLayout:
+    """The cell tags of a problem (ics tags, then ecs tags), their side, and on this rank: the owned cells sorted by tag, the
+    volume of every tag and the membrane area of every tag (facets whose membrane tag equals the cell tag, the reference's
+    ``dS(tag)``).  Volumes and areas are this rank's parts; ``ProblemKNPEMI.ion_budget`` sums them over the ranks."""
+
+    def __init__(self, problem):
+        p = problem
+        lm = p.local_mesh
+        intra = [int(t) for t in p.intra_tags]
+        extra = [int(t) for t in np.ravel(p.extra_tag)]
+        self.tags = np.array(intra + extra, dtype=np.int64)
+        self.side = np.array([0] * len(intra) + [1] * len(extra), dtype=np.int64)
+        nco = int(lm.n_cells_owned)
+        self.seg_ptr, self.cells = tag_map(lm.cell_tags[:nco], self.tags)
+        vol = cell_volumes(lm.coords, lm.cells[:nco])
+        dense = np.repeat(np.arange(len(self.tags)), np.diff(self.seg_ptr))
+        self.volume = np.bincount(dense, weights=vol[self.cells], minlength=len(self.tags))
+        self.area = np.zeros(len(self.tags))
+        own = owned_facets(p)
+        if own.any():
+            fptr, fitems = tag_map(np.asarray(p.gamma_facet_tags)[own], self.tags)
+            fdense = np.repeat(np.arange(len(self.tags)), np.diff(fptr))
+            self.area = np.bincount(fdense, weights=p._fmeas[own][fitems], minlength=len(self.tags))
+
+    @property
+    def n_tags(self):
+        return len(self.tags)
+
+
+def membrane_program(problem, expr):
+    """Compile one membrane expression with the field roles of the mechanism programs (output 0).  It may only read the
+    auxiliary fields the mechanism programs already read: the assembly's field table stays as it is."""
+    p = problem
+    roles = {}
+    for j in range(p.N_ions):
+        roles[id(p.wh[0][j])] = ("KI", j)
+        roles[id(p.wh[1][j])] = ("KE", j)
+    roles[id(p.phi_m_prev)] = ("PHIM", 0)
+    aux = list(getattr(p, "aux_functions", []))
+    n0 = len(aux)
+    spec = fem.compile_program([expr], roles, aux)
+    if len(aux) != n0:
+        raise ValueError("a diagnostic expression reads a nodal field that no membrane mechanism reads")
+    return spec

@@ -8,6 +8,7 @@ Mirrors reference
   src/CGx/KNPEMI/KNPEMIx_solver.py:551-643      init_png_savefile / save_png / init_data / save_data
   src/CGx/KNPEMI/KNPEMIx_solver.py:799-821      checkpoints of the 2(N+1) solution functions every ``save_interval`` steps
   src/CGx/KNPEMI/KNPEMIx_solver.py:833-866      export_data: file names of the ``.npy`` artefacts
+  src/CGx/KNPEMI/KNPEMIx_solver.py:578-610      stimulus current integrated over the stimulus membranes at every record (stimulus.npy)
 The reference evaluates with scifem.evaluate_function (P1 interpolation in the cell containing the point) and checkpoints with
 adios4dolfinx; here the interpolation weights are found once on the host and each evaluation is one tiny device gather, and a
 checkpoint is an ``.npz`` of the nodal arrays per rank (with the local-to-global vertex map).
@@ -155,6 +156,23 @@ class RunOutput:
             solver.gamma_point_values = np.zeros((n, len(p.gamma_points)))
         if solver.save_cpoints:
             os.makedirs(os.path.join(self.prefix, "checkpoints"), exist_ok=True)
+        # stimulus-current trace (KNPEMIx_solver.py:578-585): the expression as a diagnostic program, integrated over the stimulus
+        # membranes on the device into one slot per record; read at export (or every step when the problem prints)
+        self.stim = None
+        if self.traces and hasattr(p, "stim_ufl_expr"):
+            from .diagnostics import membrane_program
+            be = solver.backend
+            self.stim_spec = membrane_program(p, p.stim_ufl_expr)
+            be.set_diag_program(self.stim_spec)
+            be.set_facet_groups([p.stimulus_tags])
+            self.stim = torch.zeros(solver.time_steps + 1, dtype=torch.float64, device=be.device)
+        # ion amounts per cell tag every save_interval steps (output key save_ion_budget), one row of a preallocated device tensor each
+        self.budget = None
+        if getattr(solver, "save_ion_budget", False):
+            os.makedirs(self.prefix, exist_ok=True)
+            lay = solver.backend.budget_layout()
+            n_rec = solver.time_steps // solver.save_interval + 1
+            self.budget = torch.zeros((n_rec, lay.n_tags, 3), dtype=torch.float64, device=solver.backend.device)
         self.xdmf = None
         if getattr(solver, "save_xdmfs", False):
             os.makedirs(self.prefix, exist_ok=True)
@@ -181,6 +199,14 @@ class RunOutput:
             s.ics_point_values[i] = self.ics_eval(p.wh[0])
             s.ecs_point_values[i] = self.ecs_eval(p.wh[1])
             s.gamma_point_values[i] = self.gamma_eval([p.phi_m_prev])[0]
+        if self.stim is not None:                                      # KNPEMIx_solver.py:580-582, 604-610
+            be = s.backend
+            be.refresh_diag_constants(self.stim_spec)
+            be.membrane_integral(self.stim[i:i + 1])
+            if i > 0 and not getattr(p, "quiet", False):               # a read-back: only where the step timers are read anyway
+                p.print(f"Total stimulus current: {p.comm.allreduce_sum(float(self.stim[i])):.2e}")
+        if self.budget is not None and (i % s.save_interval == 0):
+            s.backend.ion_amounts(self.budget[i // s.save_interval])
         if s.save_cpoints and (i % s.save_interval == 0):
             self.checkpoint(i)
         if self.xdmf is not None and i > 0 and (i % s.save_interval == 0):       # reference :471
@@ -334,6 +360,27 @@ class RunOutput:
             np.save(out + "solve_time.npy", np.array(s.solve_time))
             if not s.direct_solver:
                 np.save(out + "iterations.npy", np.array(s.iterations))
+        if self.stim is not None:                                      # KNPEMIx_solver.py:855-857
+            stim = self._sum_ranks(self.stim.cpu().numpy())
+            if p.comm.rank == 0:
+                np.save(out + "stimulus.npy", stim)
+
+    def _sum_ranks(self, a):
+        """a summed over the ranks in rank order (the same bits for the same rank count)"""
+        if self.p.comm.size == 1:
+            return a
+        return np.sum(self.p.comm.all_gather_object(a), axis=0)
+
+    def save_ion_budget(self):
+        """ion_budget.npy: [records, cell tags, (Na, K, Cl)] in mol at steps 0, save_interval, 2 save_interval, ...;
+        ion_budget_tags.npy: per cell tag (tag, side 0 intra / 1 extra, volume [m^3], membrane area [m^2]).  One read-back."""
+        p = self.p
+        lay = self.s.backend.budget_layout()
+        data = self._sum_ranks(self.budget.cpu().numpy())
+        vol, area = self._sum_ranks(lay.volume), self._sum_ranks(lay.area)
+        if p.comm.rank == 0:
+            np.save(p.output_dir + "ion_budget.npy", data)
+            np.save(p.output_dir + "ion_budget_tags.npy", np.stack([lay.tags, lay.side, vol, area], axis=1).astype(np.float64))
 
     def figures(self):
         """PNG plots of the traces (KNPEMIx_solver.py:645-764) when matplotlib is installed; the data are exported either way."""

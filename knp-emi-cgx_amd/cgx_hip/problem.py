@@ -788,12 +788,37 @@ class ProblemKNPEMI(MixedDimensionalProblem):
         self.P_block_jacobi = bool(use_block_jacobi)
         self.P = "hard-wired in knp_kernels.hip (k_assemble_nodes<true>, k_gamma_pairs<true>)" + ("" if use_block_jacobi else " + (phi,k) blocks of A")
 
-    def print_conservation(self):
+    def ion_budget(self):
+        """Per cell tag (ics tags, then ecs tags), summed over ranks: ``tag``, ``side`` (0 intra, 1 extra), ``volume`` [m^3],
+        ``area`` [m^2] (membrane facets tagged with the cell tag, the reference's dS(tag); 0 when there are none), ``Na``, ``K``,
+        ``Cl`` [mol] and ``charge`` = F (N_Na + N_K - N_Cl) [C] (KNPEMIx_problem.py:829-840).  One device pass (knp_diag_volume_integrals)
+        and one read-back."""
+        from .diagnostics import CHARGE_VALENCES
         be = self.create_backend()
-        tot = be.total_ion_amounts()
-        self.print(f"Time {self.t.value*1e3:.2f} ms")
-        for name, v in zip(("Na+", "K+ ", "Cl-"), tot):
-            self.print(f"Total {name} concentration: {v:.2e} mol")
+        lay = be.budget_layout()
+        amounts = be.ion_amounts().cpu().numpy()
+        if self.comm.size > 1:
+            parts = self.comm.all_gather_object((amounts, lay.volume, lay.area))
+            amounts = np.sum([q[0] for q in parts], axis=0)
+            volume, area = np.sum([q[1] for q in parts], axis=0), np.sum([q[2] for q in parts], axis=0)
+        else:
+            volume, area = lay.volume.copy(), lay.area.copy()
+        charge = float(self.F.value) * (amounts @ np.array(CHARGE_VALENCES))
+        return {"tag": lay.tags.copy(), "side": lay.side.copy(), "volume": volume, "area": area,
+                "Na": amounts[:, 0].copy(), "K": amounts[:, 1].copy(), "Cl": amounts[:, 2].copy(), "charge": charge}
+
+    def print_conservation(self):
+        """Total ion amounts and, per intracellular tag, volume, membrane area and charge: the reference's lines
+        (KNPEMIx_problem.py:807-843), printed on rank 0 from ``ion_budget()``."""
+        b = self.ion_budget()
+        if self.comm.rank != 0:
+            return
+        print(f"Time {self.t.value*1e3:.2f} ms")
+        print(f"Total Na+ concentration: {b['Na'].sum():.2e} mol")
+        print(f"Total K+  concentration: {b['K'].sum():.2e} mol")
+        print(f"Total Cl- concentration: {b['Cl'].sum():.2e} mol")
+        for k in np.nonzero(b["side"] == 0)[0]:
+            print(f"  Intra tag {b['tag'][k]}: Volume = {b['volume'][k]:.2e} m^3, Area = {b['area'][k]:.2e} m^2, Charge = {b['charge'][k]:.2e} C")
 
     def print_errors(self):
         """L2 errors against the exact solution at the current time (KNPEMIx_problem.py:845-907)."""

@@ -1,0 +1,306 @@
+// Diagnostics (knp_diag_*): per-tag volume integrals of the ion fields and per-tag membrane integrals of one bytecode program.
+// Included at the end of knp_kernels.hip, after the host helpers (dev_upload, check_fields, validate_program) it uses.
+//
+// Both integrals reduce per tag without floating-point atomics.  The items (owned cells / selected membrane facets) are sorted by
+// their dense tag index on the host, once; a block takes a fixed-size chunk of consecutive items, sums each run of equal tags inside
+// the chunk with a segmented scan in LDS and stores one partial per (chunk, tag) pair at index tag + chunk (unique: consecutive
+// chunks share at most their boundary tag).  A second pass adds a tag's partials in chunk order, one wave per tag.  The work split
+// depends on the item count only, never on how the items fall into tags, and the result is the same bits on every run.
+
+// One partial per run of equal keys inside the block's chunk (keys ascending over the live threads, which form a prefix).
+template <int NV, int BT>
+__device__ __forceinline__ void diag_chunk_partials(int key, bool live, bool last_item, const double (&v)[NV], double* __restrict__ partial) {
+    __shared__ int skey[BT];
+    __shared__ double sv[NV][BT];
+    const int t = threadIdx.x;
+    skey[t] = live ? key : -1;
+#pragma unroll
+    for (int j = 0; j < NV; ++j) sv[j][t] = live ? v[j] : 0.0;
+    __syncthreads();
+    for (int d = 1; d < BT; d <<= 1) {      // inclusive segmented scan, fixed order
+        double a[NV];
+        const bool same = t >= d && skey[t - d] == skey[t];
+#pragma unroll
+        for (int j = 0; j < NV; ++j) a[j] = same ? sv[j][t - d] : 0.0;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < NV; ++j) sv[j][t] += a[j];
+        __syncthreads();
+    }
+    if (live && (last_item || t == BT - 1 || skey[t + 1] != key)) {
+#pragma unroll
+        for (int j = 0; j < NV; ++j) partial[((size_t)key + blockIdx.x) * NV + j] = sv[j][t];
+    }
+}
+
+// (a) amounts of the three ions per tag: |T|/(d+1) * sum over the cell's vertices of the fields of the cell's side (exact P1 integral)
+template <int DIM>
+__global__ void __launch_bounds__(NT) k_diag_cells(int n, const int32_t* __restrict__ item, const int32_t* __restrict__ key,
+                                                   const int32_t* __restrict__ cells, const uint8_t* __restrict__ cell_side,
+                                                   const double* __restrict__ coords, FieldPtrs f, double* __restrict__ partial) {
+    const int i = blockIdx.x * NT + threadIdx.x;
+    const bool live = i < n;
+    double v[3] = {0.0, 0.0, 0.0};
+    int k = -1;
+    if (live) {
+        const int c = item[i];
+        k = key[i];
+        int vv[DIM + 1];
+#pragma unroll
+        for (int a = 0; a <= DIM; ++a) vv[a] = cells[(size_t)c * (DIM + 1) + a];
+        double e[DIM][DIM];
+#pragma unroll
+        for (int a = 0; a < DIM; ++a)
+#pragma unroll
+            for (int b = 0; b < DIM; ++b) e[a][b] = coords[(size_t)vv[a + 1] * DIM + b] - coords[(size_t)vv[0] * DIM + b];
+        const double det = DIM == 2 ? e[0][0] * e[1][1] - e[0][1] * e[1][0]
+                                    : e[0][0] * (e[1][1] * e[2][2] - e[1][2] * e[2][1]) - e[0][1] * (e[1][0] * e[2][2] - e[1][2] * e[2][0]) +
+                                          e[0][2] * (e[1][0] * e[2][1] - e[1][1] * e[2][0]);
+        const double w = fabs(det) / (DIM == 2 ? 6.0 : 24.0);   // |T| / (d+1) = |det| / (d! (d+1))
+        const bool ext = cell_side[c] != 0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double* fj = ext ? f.ke[j] : f.ki[j];
+            double s = 0.0;
+#pragma unroll
+            for (int a = 0; a <= DIM; ++a) s += fj[vv[a]];
+            v[j] = w * s;
+        }
+    }
+    diag_chunk_partials<3, NT>(k, live, i == n - 1, v, partial);
+}
+
+// (b) integral over the selected membrane facets of the sum of a program's outputs: quadrature points q, weights q_w |F|
+static constexpr int DIAG_BT = 128;   // facets per block: the interpreter's LDS register file is [n_regs][DIAG_BT] doubles
+struct DiagConsts { double v[KNP_DIAG_MAX_CONSTS]; };
+template <int DIM>
+__global__ void __launch_bounds__(DIAG_BT) k_diag_facets(int n, const int32_t* __restrict__ item, const int32_t* __restrict__ key,
+                                                         const int32_t* __restrict__ fv, const double* __restrict__ fmeas, int n_q,
+                                                         const double* __restrict__ qp, const double* __restrict__ qw, FieldPtrs f,
+                                                         int n_aux, const double* __restrict__ coords, const int32_t* __restrict__ code,
+                                                         int n_instr, DiagConsts K, int n_consts, double* __restrict__ partial) {
+    extern __shared__ double dsmem[];     // register file of the interpreter
+    __shared__ double sk[KNP_DIAG_MAX_CONSTS];
+    for (int i = threadIdx.x; i < n_consts; i += DIAG_BT) sk[i] = K.v[i];
+    __syncthreads();
+    const int i = blockIdx.x * DIAG_BT + threadIdx.x;
+    const bool live = i < n;
+    const int ii = live ? i : n - 1;      // idle lanes shadow the last facet with weight zero: the interpreter's wave stays uniform
+    const int g = item[ii];
+    int v[DIM];
+#pragma unroll
+    for (int a = 0; a < DIM; ++a) v[a] = fv[(size_t)g * DIM + a];
+    const double meas = live ? fmeas[g] : 0.0;
+    double* reg = dsmem + threadIdx.x;
+    double acc = 0.0;
+    for (int q = 0; q < n_q; ++q) {
+        double lam[DIM];
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) lam[a] = qp[q * DIM + a];
+        double kiq[1][3], keq[1][3], phq[1] = {0.0}, auxq[1][KNP_MAX_AUX], xq[1][3], Iout[1][3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            double si = 0.0, se = 0.0;
+#pragma unroll
+            for (int a = 0; a < DIM; ++a) {
+                si += lam[a] * f.ki[j][v[a]];
+                se += lam[a] * f.ke[j][v[a]];
+            }
+            kiq[0][j] = si;
+            keq[0][j] = se;
+            Iout[0][j] = 0.0;
+        }
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) phq[0] += lam[a] * f.phim[v[a]];
+        for (int k = 0; k < n_aux; ++k) {
+            double t = 0.0;
+#pragma unroll
+            for (int a = 0; a < DIM; ++a) t += lam[a] * f.aux[k][v[a]];
+            auxq[0][k] = t;
+        }
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            double t = 0.0;
+            if (d < DIM) {
+#pragma unroll
+                for (int a = 0; a < DIM; ++a) t += lam[a] * coords[(size_t)v[a] * DIM + d];
+            }
+            xq[0][d] = t;
+        }
+        run_program<1, DIAG_BT>(code, n_instr, sk, kiq, keq, phq, auxq, xq, Iout, reg);
+        acc += qw[q] * meas * (Iout[0][0] + Iout[0][1] + Iout[0][2]);
+    }
+    const double val[1] = {acc};
+    diag_chunk_partials<1, DIAG_BT>(live ? key[i] : -1, live, i == n - 1, val, partial);
+}
+
+// a tag's partials in chunk order, one wave per tag; empty tags give zero
+template <int NV>
+__global__ void __launch_bounds__(NT) k_diag_combine(int n_tags, int chunk, const int32_t* __restrict__ seg_ptr,
+                                                     const double* __restrict__ partial, double* __restrict__ out) {
+    const int s = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (s >= n_tags) return;              // whole waves
+    const int lo = seg_ptr[s], hi = seg_ptr[s + 1];
+    double acc[NV];
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc[j] = 0.0;
+    if (hi > lo) {
+        const int b1 = (hi - 1) / chunk;
+        for (int b = lo / chunk + lane; b <= b1; b += 64)
+#pragma unroll
+            for (int j = 0; j < NV; ++j) acc[j] += partial[((size_t)s + b) * NV + j];
+    }
+#pragma unroll
+    for (int j = 0; j < NV; ++j) acc[j] = wave_sum(acc[j]);
+    if (lane == 0)
+#pragma unroll
+        for (int j = 0; j < NV; ++j) out[(size_t)s * NV + j] = acc[j];
+}
+
+static void diag_map_free(KnpDiagMap& m) {
+    dev_free(m.d_ptr); dev_free(m.d_item); dev_free(m.d_key); dev_free(m.d_partial);
+    m = KnpDiagMap();
+}
+void knp_diag_free(knp_ctx* ctx) {
+    diag_map_free(ctx->diag_cells);
+    diag_map_free(ctx->diag_facets);
+    dev_free(ctx->diag_code);
+    ctx->diag_n_instr = ctx->diag_n_regs = ctx->diag_n_consts = 0;
+    ctx->diag_prog = false;
+}
+
+// validate a host tag map (items in [0, n_items), each at most once, seg_ptr non-decreasing from 0) and upload it with its scratch
+static int diag_map_set(knp_ctx* ctx, KnpDiagMap& m, int n_tags, const int32_t* seg_ptr, const int32_t* items, int n_items, int chunk,
+                        int nv, const char* what) {
+    if (n_tags < 0 || (n_tags > 0 && !seg_ptr)) { ctx->err = std::string(what) + ": bad tag count or null seg_ptr"; return KNP_E_ARG; }
+    const int n = n_tags > 0 ? seg_ptr[n_tags] : 0;
+    if (n_tags > 0 && seg_ptr[0] != 0) { ctx->err = std::string(what) + ": seg_ptr[0] must be 0"; return KNP_E_ARG; }
+    if (n < 0 || n > n_items || (n > 0 && !items)) { ctx->err = std::string(what) + ": more items than the mesh has, or null items"; return KNP_E_ARG; }
+    std::vector<int32_t> key((size_t)n);
+    std::vector<uint8_t> seen((size_t)std::max(n_items, 1), 0);
+    for (int s = 0; s < n_tags; ++s) {
+        if (seg_ptr[s + 1] < seg_ptr[s]) { ctx->err = std::string(what) + ": seg_ptr must be non-decreasing"; return KNP_E_ARG; }
+        for (int i = seg_ptr[s]; i < seg_ptr[s + 1]; ++i) {
+            const int it = items[i];
+            if (it < 0 || it >= n_items || seen[it]) { ctx->err = std::string(what) + ": item out of range or listed twice"; return KNP_E_ARG; }
+            seen[it] = 1;
+            key[i] = s;
+        }
+    }
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // a diagnostic in flight may still read the old map
+    diag_map_free(m);
+    std::vector<int32_t> ptr(seg_ptr, seg_ptr + (n_tags > 0 ? n_tags + 1 : 0));
+    std::vector<int32_t> itv(items, items + n);
+    KCHK(dev_upload(ctx, &m.d_ptr, ptr));
+    KCHK(dev_upload(ctx, &m.d_item, itv));
+    KCHK(dev_upload(ctx, &m.d_key, key));
+    m.n_tags = n_tags;
+    m.n = n;
+    m.chunk = chunk;
+    m.n_chunks = (n + chunk - 1) / chunk;
+    const size_t np = (size_t)(n_tags + m.n_chunks) * nv;
+    HIPCHK(hipMalloc((void**)&m.d_partial, std::max<size_t>(np, 1) * sizeof(double)));
+    return KNP_OK;
+}
+
+static int diag_combine(knp_ctx* ctx, const KnpDiagMap& m, int nv, double* out) {
+    if (m.n_tags == 0) return KNP_OK;
+    const unsigned nb = (unsigned)((m.n_tags + NT / 64 - 1) / (NT / 64));
+    if (nv == 3)
+        hipLaunchKernelGGL(k_diag_combine<3>, dim3(nb), dim3(NT), 0, ctx->stream, m.n_tags, m.chunk, m.d_ptr, m.d_partial, out);
+    else
+        hipLaunchKernelGGL(k_diag_combine<1>, dim3(nb), dim3(NT), 0, ctx->stream, m.n_tags, m.chunk, m.d_ptr, m.d_partial, out);
+    HIPCHK(hipGetLastError());
+    return KNP_OK;
+}
+
+extern "C" {
+
+int knp_diag_set_cell_tags(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr, const int32_t* cells) {
+    CHECK_CTX(ctx);
+    return diag_map_set(ctx, ctx->diag_cells, n_tags, seg_ptr, cells, ctx->g.n_c_owned, NT, 3, "cell tag map");
+}
+
+int knp_diag_volume_integrals(knp_ctx* ctx, const knp_fields* fields, double* out) {
+    CHECK_CTX(ctx);
+    KCHK(check_fields(ctx, fields, false));
+    if (!out) { ctx->err = "null output buffer"; return KNP_E_ARG; }
+    const KnpDiagMap& m = ctx->diag_cells;
+    if (!m.d_ptr) { ctx->err = "no cell tag map (knp_diag_set_cell_tags)"; return KNP_E_STATE; }
+    const FieldPtrs f = make_fields(fields);
+    if (m.n > 0) {
+        if (ctx->g.dim == 2)
+            hipLaunchKernelGGL(k_diag_cells<2>, dim3(m.n_chunks), dim3(NT), 0, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_cells,
+                               ctx->d_cell_side, ctx->d_coords, f, m.d_partial);
+        else
+            hipLaunchKernelGGL(k_diag_cells<3>, dim3(m.n_chunks), dim3(NT), 0, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_cells,
+                               ctx->d_cell_side, ctx->d_coords, f, m.d_partial);
+        HIPCHK(hipGetLastError());
+    }
+    return diag_combine(ctx, m, 3, out);
+}
+
+int knp_diag_set_facet_tags(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr, const int32_t* facets) {
+    CHECK_CTX(ctx);
+    return diag_map_set(ctx, ctx->diag_facets, n_tags, seg_ptr, facets, ctx->g.n_g, DIAG_BT, 1, "facet tag map");
+}
+
+int knp_diag_set_program(knp_ctx* ctx, int32_t n_instr, const int32_t* code, int32_t n_consts, const double* consts) {
+    CHECK_CTX(ctx);
+    if (n_instr < 0 || (n_instr && !code) || n_consts < 0 || n_consts > KNP_DIAG_MAX_CONSTS || (n_consts && !consts)) {
+        ctx->err = "bad diagnostic program arguments (at most " + std::to_string(KNP_DIAG_MAX_CONSTS) + " constants)";
+        return KNP_E_ARG;
+    }
+    int n_regs = 0;
+    KCHK(validate_program(ctx, n_instr, code, n_consts, &n_regs));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    dev_free(ctx->diag_code);
+    KCHK(dev_upload_raw(ctx, &ctx->diag_code, code, (size_t)4 * n_instr));
+    ctx->diag_n_instr = n_instr;
+    ctx->diag_n_regs = n_regs;
+    ctx->diag_n_consts = n_consts;
+    for (int i = 0; i < n_consts; ++i) ctx->diag_consts[i] = consts[i];
+    ctx->diag_prog = true;
+    return KNP_OK;
+}
+
+int knp_diag_set_program_constants(knp_ctx* ctx, int32_t n_consts, const double* consts) {
+    CHECK_CTX(ctx);
+    if (!ctx->diag_prog || n_consts != ctx->diag_n_consts || (n_consts && !consts)) { ctx->err = "diagnostic program / constant count mismatch"; return KNP_E_ARG; }
+    for (int i = 0; i < n_consts; ++i) ctx->diag_consts[i] = consts[i];   // kernel arguments of the next launch: nothing to copy
+    return KNP_OK;
+}
+
+int knp_diag_membrane_integral(knp_ctx* ctx, const knp_fields* fields, double* out) {
+    CHECK_CTX(ctx);
+    KCHK(check_fields(ctx, fields, true));
+    if (!out) { ctx->err = "null output buffer"; return KNP_E_ARG; }
+    const KnpDiagMap& m = ctx->diag_facets;
+    if (!m.d_ptr) { ctx->err = "no facet tag map (knp_diag_set_facet_tags)"; return KNP_E_STATE; }
+    if (!ctx->diag_prog) { ctx->err = "no diagnostic program (knp_diag_set_program)"; return KNP_E_STATE; }
+    int n_aux = 0;
+    for (int k = 0; k < KNP_MAX_AUX; ++k)
+        if (fields->aux[k]) n_aux = k + 1;
+    for (int k = 0; k < n_aux; ++k)
+        if (!fields->aux[k]) { ctx->err = "aux fields must be contiguous from index 0"; return KNP_E_ARG; }
+    if (m.n > 0) {
+        const FieldPtrs f = make_fields(fields);
+        DiagConsts K;
+        for (int i = 0; i < KNP_DIAG_MAX_CONSTS; ++i) K.v[i] = i < ctx->diag_n_consts ? ctx->diag_consts[i] : 0.0;
+        const size_t lds = (size_t)std::max(ctx->diag_n_regs, 1) * DIAG_BT * sizeof(double);   // <= 48 registers: 48 KiB
+        const int n_q = ctx->g.n_q;
+        if (ctx->g.dim == 2)
+            hipLaunchKernelGGL(k_diag_facets<2>, dim3(m.n_chunks), dim3(DIAG_BT), lds, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_fv,
+                               ctx->d_fmeas, n_q, ctx->d_qp, ctx->d_qw, f, n_aux, ctx->d_coords, ctx->diag_code, ctx->diag_n_instr, K,
+                               ctx->diag_n_consts, m.d_partial);
+        else
+            hipLaunchKernelGGL(k_diag_facets<3>, dim3(m.n_chunks), dim3(DIAG_BT), lds, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_fv,
+                               ctx->d_fmeas, n_q, ctx->d_qp, ctx->d_qw, f, n_aux, ctx->d_coords, ctx->diag_code, ctx->diag_n_instr, K,
+                               ctx->diag_n_consts, m.d_partial);
+        HIPCHK(hipGetLastError());
+    }
+    return diag_combine(ctx, m, 1, out);
+}
+
+}  // extern "C"

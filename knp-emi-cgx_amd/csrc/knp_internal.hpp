@@ -59,6 +59,16 @@ int knp_build_csr_pattern(KnpHostGraph& g);
 struct knp_ctx;
 void knp_jit_build(knp_ctx* ctx);
 void knp_jit_release(knp_ctx* ctx);
+void knp_diag_free(knp_ctx* ctx);
+
+// ---- tag map of a diagnostic reduction (knp_diagnostics.inc): items sorted by dense tag index --------------------------------
+struct KnpDiagMap {
+    int n_tags = 0, n = 0, chunk = 0, n_chunks = 0;
+    int32_t* d_ptr = nullptr;      // [n_tags+1] segment offsets
+    int32_t* d_item = nullptr;     // [n] cell / facet ids, sorted by tag
+    int32_t* d_key = nullptr;      // [n] tag index of every item
+    double* d_partial = nullptr;   // [(n_tags + n_chunks) * values] per (chunk, tag) partial sums
+};
 
 // ---- device-side program ------------------------------------------------------------------
 struct KnpProgram {
@@ -356,6 +366,12 @@ struct knp_ctx {
     // step timers (knp_timer_mark / knp_timer_read): timing events recorded on the main stream, read back in one go
     std::vector<hipEvent_t> tm_events;
     size_t tm_used = 0;
+    // diagnostics (knp_diag_*): per-tag ion amounts and membrane integrals of one program, outside the assembly's program table
+    KnpDiagMap diag_cells, diag_facets;
+    int32_t* diag_code = nullptr;
+    int diag_n_instr = 0, diag_n_regs = 0, diag_n_consts = 0;
+    double diag_consts[KNP_DIAG_MAX_CONSTS] = {};   // host copy: passed to the kernel by value at every launch
+    bool diag_prog = false;
     // profiling
     int prof_on = 0;
     std::vector<hipEvent_t> prof_pool;   // recycled timing events

@@ -3109,6 +3109,7 @@ int knp_destroy(knp_ctx* ctx) {
     dev_free(ctx->d_p_vals_f);
     dev_free(ctx->d_ML); dev_free(ctx->d_cc); dev_free(ctx->d_t2); dev_free(ctx->d_w2);
     dev_free(ctx->d_defl_mode); dev_free(ctx->d_defl_einv); dev_free(ctx->d_bc_dofs);
+    knp_diag_free(ctx);
     delete ctx;
     return KNP_OK;
 }
@@ -5690,3 +5691,6 @@ int knp_get_stats(const knp_ctx* ctx, double* out) {
 }
 
 }  // extern "C"
+
+// per-tag diagnostics: ion amounts per cell tag, membrane integrals of one program (knp_diag_*)
+#include "knp_diagnostics.inc"
