@@ -487,14 +487,17 @@ class Backend:
         """Start ||B b|| of the next solve on the library's side stream (b must be final); overlaps the matrix assembly."""
         self.check(self.lib.knp_gmres_prepare(self.ctx, C.c_void_p(self.b.data_ptr())))
 
-    def gmres(self, rtol, atol=1e-50, max_it=5000, restart=30):
+    def _ksp_solve(self, fn, rtol, atol, max_it, restart):
+        """one of the library's Krylov drivers on (b, x): iterations, last residual estimate, reason code"""
         its = C.c_int32()
         rn = C.c_double()
         reason = C.c_int32()
-        self.check(self.lib.knp_gmres_solve(self.ctx, C.c_void_p(self.b.data_ptr()), C.c_void_p(self.x.data_ptr()),
-                                            float(rtol), float(atol), int(max_it), int(restart), C.byref(its),
-                                            C.byref(rn), C.byref(reason)))
+        self.check(fn(self.ctx, C.c_void_p(self.b.data_ptr()), C.c_void_p(self.x.data_ptr()), float(rtol), float(atol), int(max_it),
+                      int(restart), C.byref(its), C.byref(rn), C.byref(reason)))
         return its.value, rn.value, reason.value
+
+    def gmres(self, rtol, atol=1e-50, max_it=5000, restart=30):
+        return self._ksp_solve(self.lib.knp_gmres_solve, rtol, atol, max_it, restart)
 
     def fgmres_prepare(self):
         """Start ||b|| of the next flexible solve on the library's side stream (b must be final); overlaps the matrix assembly."""
@@ -502,13 +505,7 @@ class Backend:
 
     def fgmres(self, rtol, atol=1e-50, max_it=5000, restart=30):
         """Flexible GMRES (right preconditioning): stops on the true residual, ||b - A x|| <= max(rtol ||b||, atol)."""
-        its = C.c_int32()
-        rn = C.c_double()
-        reason = C.c_int32()
-        self.check(self.lib.knp_fgmres_solve(self.ctx, C.c_void_p(self.b.data_ptr()), C.c_void_p(self.x.data_ptr()),
-                                             float(rtol), float(atol), int(max_it), int(restart), C.byref(its),
-                                             C.byref(rn), C.byref(reason)))
-        return its.value, rn.value, reason.value
+        return self._ksp_solve(self.lib.knp_fgmres_solve, rtol, atol, max_it, restart)
 
     def matrix_max_abs(self) -> float:
         """max |A_ij| over the locally stored entries (device reduction over the pair-major arrays)."""

@@ -199,6 +199,18 @@ struct KnpAmgHier {
     float *pt_f = nullptr, *pt_phi_f = nullptr;
 };
 
+// What the side stream holds for the next solve.  LEFT_ENQUEUED: ||B b|| of knp_gmres_prepare was enqueued on it.  Concurrent form
+// (one GPU, fused cycle, null space on): the side-stream cycle works on its OWN vectors, partial sums and reduction slots, so it may
+// still be running while the solve computes its first preconditioned residual on the main stream; the solve only joins it when it
+// needs ||B b||, after its first read-back.  LEFT_DEFERRED: only the fork point is recorded, the solve enqueues the cycle behind
+// its own first residual chain; LEFT_CONCURRENT: it has.  FLEX: ||b|| of knp_fgmres_prepare.
+struct KnpSidePrep {
+    enum Kind { NONE, LEFT_ENQUEUED, LEFT_DEFERRED, LEFT_CONCURRENT, FLEX } kind = NONE;
+    const double* b = nullptr;   // the right-hand side it was started for
+    bool fused = false;          // LEFT_ENQUEUED: it used the one-reduction projected norm (flag in slot 61)
+    bool left() const { return kind != NONE && kind != FLEX; }
+};
+
 struct knp_ctx {
     std::string err;
     hipStream_t stream = nullptr;
@@ -341,17 +353,10 @@ struct knp_ctx {
     int32_t *d_nodes_int = nullptr, *d_nodes_bnd = nullptr;
     hipStream_t stream3 = nullptr;
     hipEvent_t ev_x = nullptr, ev_halo = nullptr;
-    // side stream for ||B b|| of the next solve (knp_gmres_prepare)
+    // side stream for the norm of the next solve's right-hand side (knp_gmres_prepare: ||B b||, knp_fgmres_prepare: ||b||)
     hipStream_t stream2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    const double* prep_b = nullptr;
-    const double* fprep_b = nullptr;   // ||b|| of the next knp_fgmres_solve is being computed on the side stream (knp_fgmres_prepare)
-    int prep_fused = 0;   // the side-stream ||B b|| used the one-reduction projected norm (flag in slot 61)
-    // Concurrent form (one GPU, fused cycle, null space on): the side-stream cycle works on its OWN vectors, partial sums and
-    // reduction slots, so it may still be running while the solve computes its first preconditioned residual on the main
-    // stream; the solve only joins it when it needs ||B b||, after its first read-back.
-    int prep_conc = 0;
-    bool prep_deferred = false;   // concurrent form: the side-stream cycle is enqueued by the solve, behind its own first residual chain
+    KnpSidePrep prep;
     bool side_ws = false;
     double *d_t2_s = nullptr, *d_w2_s = nullptr, *d_wb = nullptr, *d_partial_s = nullptr;
     // matrix assembly on its own stream (knp_assemble_matrix_async): independent of the right-hand side chain of the same step
