@@ -33,6 +33,8 @@
  *        assemble_scalar(k*dx(tag)) per ion and cell tag of print_conservation (KNPEMIx_problem.py:821-840)
  *   knp_diag_set_facet_tags / knp_diag_set_program / knp_diag_set_program_constants / knp_diag_membrane_integral
  *        assemble_scalar(stim_ufl_expr*dS(stimulus_tags)) of the stimulus trace (KNPEMIx_solver.py:580-582, 605-607)
+ *   knp_diag_set_flux_facets / knp_diag_membrane_fluxes
+ *        assemble_scalar of the six forms of create_flux_forms (utils/calc_fluxes.py:70-90), per membrane tag
  *   knp_set_comm                     the MPI calls hidden in PETSc/DOLFINx (ghost updates
  *                                    KNPEMIx_solver.py:439,459,468; Allreduce inside KSPSolve)
  *
@@ -370,6 +372,24 @@ int knp_diag_set_program(knp_ctx* ctx, int32_t n_instr, const int32_t* code /* h
                          const double* consts /* host */);
 int knp_diag_set_program_constants(knp_ctx* ctx, int32_t n_consts, const double* consts /* host */);
 int knp_diag_membrane_integral(knp_ctx* ctx, const knp_fields* fields, double* out /* device [n_tags] */);
+/* knp_diag_set_flux_facets: a tag map of membrane facets like knp_diag_set_facet_tags, kept apart from it (both may be live), and an
+ *   optional axis-aligned box mask: box_lo / box_hi are host [3] (axes >= dim ignored, -inf / +inf leave an axis open) or both NULL.
+ *   Builds on the host (OpenMP) and uploads one time-invariant record per listed facet: the vertices of its intracellular cell T+
+ *   (gamma column 0) and extracellular cell T- (column 2), g_a = grad(lambda_a) . n per side (n_0 the unit normal out of T+,
+ *   n_1 = -n_0), W0 = |F| sum_q q_w m(x_q) and W_b = |F| sum_q q_w m(x_q) lambda_b(q) with m = 1 where lo < x < hi on every axis (strict),
+ *   else 0, at the points of the mesh's facet rule.  128 bytes per facet in 3D, 112 in 2D.  Synchronous.  KNP_E_MESH when a listed
+ *   facet's T- does not contain the facet or a cell is flat; the map is then unset.
+ * knp_diag_membrane_fluxes: the molar flux of ion k out of side s (0 intra, 1 extra) through the facets of tag t [mol/s],
+ *   out[6t + 3s + k] = sum_F -D[k] (W0 sum_a g_a c(v_a) + z_over_psi[k] (sum_b W_b c(f_b)) (sum_a g_a phi(v_a)))
+ *   with c = fields->k_i[k], phi = phi_i on T+ for s = 0 and c = fields->k_e[k], phi = phi_e on T- for s = 1: the integral over the
+ *   facets of mask * (-D_k (grad c_k + (z_k/psi) c_k grad phi)) . n_s of create_flux_forms (utils/calc_fluxes.py:85-88); positive = ions
+ *   leave that side's domain.  D and z_over_psi are host [3] and travel as kernel arguments.  fields->phi_m and aux are not read. */
+int knp_diag_set_flux_facets(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr /* host [n_tags+1] */,
+                             const int32_t* facets /* host [seg_ptr[n_tags]] */, const double* box_lo /* host [3] or NULL */,
+                             const double* box_hi /* host [3] or NULL */);
+int knp_diag_membrane_fluxes(knp_ctx* ctx, const knp_fields* fields, const double* phi_i /* device [n_vertices] */,
+                             const double* phi_e /* device [n_vertices] */, const double* D /* host [3] */,
+                             const double* z_over_psi /* host [3] */, double* out /* device [n_tags*6] */);
 
 /* ---- instrumentation ---- */
 /* elapsed ms and launch count of a kernel class since the last reset (HIP events on the ctx stream).

@@ -549,15 +549,8 @@ class Backend:
     def set_facet_groups(self, groups):
         """Membrane facets of this rank (owner of the first vertex) whose membrane tag is in ``groups[t]``, reduced into slot t
         of ``membrane_integral``; a facet goes to the first group that lists its tag"""
-        from .diagnostics import owned_facets, tag_map
-        p = self.p
-        own = np.nonzero(owned_facets(p))[0]
-        ftags = np.asarray(p.gamma_facet_tags)[own]
-        group_of = np.full(len(own), -1, dtype=np.int64)
-        for t, tags in reversed(list(enumerate(groups))):
-            group_of[np.isin(ftags, list(tags))] = t
-        seg_ptr, items = tag_map(group_of, np.arange(len(groups)))
-        facets = np.ascontiguousarray(own[items], dtype=np.int32)
+        from .diagnostics import facet_group_map
+        seg_ptr, facets = facet_group_map(self.p, groups)
         self.check(self.lib.knp_diag_set_facet_tags(self.ctx, len(groups), _i32(seg_ptr), _i32(facets) if facets.size else None))
         self._keep += [seg_ptr, facets]
         self.n_facet_groups = len(groups)
@@ -578,6 +571,41 @@ class Backend:
         assert out.is_contiguous() and out.dtype == torch.float64 and out.numel() == self.n_facet_groups
         f = self.fields()
         self.check(self.lib.knp_diag_membrane_integral(self.ctx, C.byref(f), C.c_void_p(out.data_ptr())))
+        return out
+
+    def set_flux_groups(self, groups, mask=None):
+        """Membrane facets of this rank (owner of the first vertex) whose membrane tag is in ``groups[t]``, reduced into slot t of
+        ``membrane_fluxes``; ``mask``: None or an open box ``(lo, hi)`` in metres (``diagnostics.stimulus_box``).  Builds the
+        per-facet records (knp_diag_set_flux_facets); a call with the groups and mask already set does nothing.  The map is
+        apart from the one of ``set_facet_groups``."""
+        from .diagnostics import facet_areas, facet_group_map
+        groups = tuple(tuple(int(t) for t in g) for g in groups)
+        box = None if mask is None else (np.ascontiguousarray(mask[0], dtype=np.float64), np.ascontiguousarray(mask[1], dtype=np.float64))
+        key = (groups, None if box is None else (box[0].tobytes(), box[1].tobytes()))
+        if getattr(self, "_flux_key", None) == key:
+            return
+        seg_ptr, facets = facet_group_map(self.p, groups)
+        self._flux_key = None
+        self.check(self.lib.knp_diag_set_flux_facets(self.ctx, len(groups), _i32(seg_ptr), _i32(facets) if facets.size else None,
+                                                     _f64(box[0]) if box else None, _f64(box[1]) if box else None))
+        self._flux_key = key
+        self.n_flux_groups = len(groups)
+        self.flux_area = facet_areas(self.p, seg_ptr, facets)
+
+    def membrane_fluxes(self, out=None):
+        """This rank's molar flux of every ion out of each side through each facet group, [n_groups, 2 (intra, extra), 3] on the
+        device in mol/s: enqueued, not waited for.  ``out``: a contiguous float64 device tensor of that size, else a new one."""
+        from .diagnostics import flux_coefficients
+        p = self.p
+        if getattr(self, "_flux_key", None) is None:
+            raise KnpError("membrane_fluxes() before set_flux_groups()")
+        if out is None:
+            out = torch.empty((self.n_flux_groups, 2, 3), dtype=torch.float64, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.float64 and out.numel() == 6 * self.n_flux_groups
+        D, zp = flux_coefficients(p)
+        f = self.fields()
+        self.check(self.lib.knp_diag_membrane_fluxes(self.ctx, C.byref(f), C.c_void_p(p.wh[0][p.N_ions].data_ptr()),
+                                                     C.c_void_p(p.wh[1][p.N_ions].data_ptr()), _f64(D), _f64(zp), C.c_void_p(out.data_ptr())))
         return out
 
     # ---- exports (parity hooks) ------------------------------------------------------------

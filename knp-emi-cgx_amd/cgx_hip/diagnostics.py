@@ -1,5 +1,6 @@
 """Per-tag diagnostics of a run: ion amounts, charge, volume and membrane area per cell tag (reference
-KNPEMIx_problem.py:807-843, ``print_conservation``) and the stimulus-current trace (KNPEMIx_solver.py:578-585, 604-610, 855-857).
+KNPEMIx_problem.py:807-843, ``print_conservation``), the stimulus-current trace (KNPEMIx_solver.py:578-585, 604-610, 855-857) and the
+trans-membrane ion fluxes per membrane tag (utils/calc_fluxes.py; KNPEMIx_solver.py:626-627, 641-643).
 
 The tag maps and the time-invariant measures are built here, on the host, once; the integrals of the fields are HIP kernels
 (csrc/knp_diagnostics.inc, ``knp_diag_*``) that run on the library's stream and write device buffers.  Reading a result is the
@@ -49,6 +50,51 @@ def owned_facets(problem):
     if not len(problem._fv):
         return np.zeros(0, dtype=bool)
     return problem._fv[:, 0] < lm.n_vertices_owned
+
+
+def facet_group_map(problem, groups):
+    """This rank's membrane facets (``owned_facets``) whose membrane tag is in ``groups[t]``, sorted by t: ``seg_ptr``
+    [len(groups) + 1] and ``facets`` (indices into the mesh's gamma list), int32.  A facet goes to the first group that lists its
+    tag; a group none of whose tags has an owned facet keeps an empty segment."""
+    p = problem
+    own = np.nonzero(owned_facets(p))[0]
+    ftags = np.asarray(p.gamma_facet_tags)[own]
+    group_of = np.full(len(own), -1, dtype=np.int64)
+    for t, tags in reversed(list(enumerate(groups))):
+        group_of[np.isin(ftags, list(tags))] = t
+    seg_ptr, items = tag_map(group_of, np.arange(len(groups)))
+    return seg_ptr, np.ascontiguousarray(own[items], dtype=np.int32)
+
+
+def stimulus_box(problem):
+    """The stimulus region as an open box ``(lo, hi)``, two float64 [3] in metres with -inf / +inf on the axes it leaves free
+    (the mask of the flux forms, utils/calc_fluxes.py:36-68); None without a ``stimulus_region``."""
+    p = problem
+    if not getattr(p, "stimulus_region", False):
+        return None
+    lo, hi = np.full(3, -np.inf), np.full(3, np.inf)
+    if p.multiple_stimulus_directions:
+        pairs = [(ax, p.stimulus_region_range[i]) for i, ax in enumerate(p.stimulus_region_directions)]
+    else:
+        pairs = [(p.stimulus_region_direction, p.stimulus_region_range)]
+    for ax, rng in pairs:                     # a product of indicator functions: an axis listed twice keeps the intersection
+        lo[ax], hi[ax] = max(lo[ax], float(rng[0])), min(hi[ax], float(rng[1]))
+    return lo, hi
+
+
+def flux_coefficients(problem):
+    """``D_k`` and ``z_k / psi`` of the flux forms as they are now (both sides use the ion's ``Di``, utils/calc_fluxes.py:79)"""
+    p = problem
+    psi = float(p.psi.value)
+    D = np.array([float(ion["Di"].value) for ion in p.ion_list], dtype=np.float64)
+    zp = np.array([float(ion["z"].value) / psi for ion in p.ion_list], dtype=np.float64)
+    return D, zp
+
+
+def facet_areas(problem, seg_ptr, facets):
+    """area of every segment of a facet map (this rank's part)"""
+    dense = np.repeat(np.arange(len(seg_ptr) - 1), np.diff(seg_ptr))
+    return np.bincount(dense, weights=problem._fmeas[facets], minlength=len(seg_ptr) - 1).astype(np.float64)
 
 
 class BudgetLayout:

@@ -173,6 +173,14 @@ class RunOutput:
             lay = solver.backend.budget_layout()
             n_rec = solver.time_steps // solver.save_interval + 1
             self.budget = torch.zeros((n_rec, lay.n_tags, 3), dtype=torch.float64, device=solver.backend.device)
+        # molar ion fluxes across the membrane-data tag inside the stimulus region at every step (output key save_fluxes): the
+        # reference's flux_values[time_steps + 1, 2 N_ions] (KNPEMIx_solver.py:626-627, 641-643), one row of a device tensor per record
+        self.fluxes = None
+        if getattr(solver, "save_fluxes", False):
+            from .fluxes import FluxEvaluator
+            os.makedirs(self.prefix, exist_ok=True)
+            self.flux_eval = FluxEvaluator(p, [p.membrane_data_tag], mask=True)
+            self.fluxes = torch.zeros((solver.time_steps + 1, 2 * p.N_ions), dtype=torch.float64, device=solver.backend.device)
         self.xdmf = None
         if getattr(solver, "save_xdmfs", False):
             os.makedirs(self.prefix, exist_ok=True)
@@ -205,6 +213,8 @@ class RunOutput:
             be.membrane_integral(self.stim[i:i + 1])
             if i > 0 and not getattr(p, "quiet", False):               # a read-back: only where the step timers are read anyway
                 p.print(f"Total stimulus current: {p.comm.allreduce_sum(float(self.stim[i])):.2e}")
+        if self.fluxes is not None:
+            self.flux_eval.enqueue(self.fluxes[i])
         if self.budget is not None and (i % s.save_interval == 0):
             s.backend.ion_amounts(self.budget[i // s.save_interval])
         if s.save_cpoints and (i % s.save_interval == 0):
@@ -381,6 +391,13 @@ class RunOutput:
         if p.comm.rank == 0:
             np.save(p.output_dir + "ion_budget.npy", data)
             np.save(p.output_dir + "ion_budget_tags.npy", np.stack([lay.tags, lay.side, vol, area], axis=1).astype(np.float64))
+
+    def save_fluxes(self):
+        """fluxes.npy: [time_steps + 1, (Na, K, Cl out of the intracellular side, Na, K, Cl out of the extracellular side)] in mol/s
+        through the membrane-data tag inside the stimulus region, state after step i in row i.  One read-back."""
+        data = self._sum_ranks(self.fluxes.cpu().numpy())
+        if self.p.comm.rank == 0:
+            np.save(self.p.output_dir + "fluxes.npy", data)
 
     def figures(self):
         """PNG plots of the traces (KNPEMIx_solver.py:645-764) when matplotlib is installed; the data are exported either way."""

@@ -807,6 +807,24 @@ class ProblemKNPEMI(MixedDimensionalProblem):
         return {"tag": lay.tags.copy(), "side": lay.side.copy(), "volume": volume, "area": area,
                 "Na": amounts[:, 0].copy(), "K": amounts[:, 1].copy(), "Cl": amounts[:, 2].copy(), "charge": charge}
 
+    def membrane_fluxes(self, tags=None, mask=False):
+        """Per membrane tag in ``tags`` (default: every tag of ``gamma_tags``, each on its own), summed over ranks: ``tag``,
+        ``area`` [m^2] (unmasked) and the molar fluxes ``flux_i`` / ``flux_e`` [n_tags, (Na, K, Cl)] in mol/s out of the
+        intracellular / extracellular domain through that membrane,
+        int_Gamma(tag) m (-D_k (grad c_k + (z_k/psi) c_k grad phi)) . n dS with the side's fields and outward normal (the forms of
+        utils/calc_fluxes.py).  ``mask=True`` restricts the integrals to the stimulus region (m of calc_fluxes.py:36-68); the region
+        is ignored when the problem has none.  One launch pair (knp_diag_membrane_fluxes) and one read-back."""
+        from .diagnostics import stimulus_box
+        be = self.create_backend()
+        tags = [int(t) for t in (self.gamma_tags if tags is None else tags)]
+        be.set_flux_groups([[t] for t in tags], stimulus_box(self) if mask else None)
+        flux = be.membrane_fluxes().cpu().numpy()
+        area = be.flux_area.copy()
+        if self.comm.size > 1:
+            parts = self.comm.all_gather_object((flux, area))
+            flux, area = np.sum([q[0] for q in parts], axis=0), np.sum([q[1] for q in parts], axis=0)
+        return {"tag": np.array(tags, dtype=np.int64), "area": area, "flux_i": flux[:, 0, :].copy(), "flux_e": flux[:, 1, :].copy()}
+
     def print_conservation(self):
         """Total ion amounts and, per intracellular tag, volume, membrane area and charge: the reference's lines
         (KNPEMIx_problem.py:807-843), printed on rank 0 from ``ion_budget()``."""

@@ -75,6 +75,7 @@ class SolverKNPEMI:
     strong_threshold = 0.5
     save_interval = 20
     save_ion_budget = False   # output key save_ion_budget: ion amounts per cell tag every save_interval steps (ion_budget.npy)
+    save_fluxes = False       # output key save_fluxes: ion fluxes across the membrane-data tag at every step (fluxes.npy)
     tot_its = 0.0
     tot_assembly_time = 0.0
     tot_solver_time = 0.0
@@ -110,6 +111,7 @@ class SolverKNPEMI:
         self.save_dat = out.get("save_dat", False)
         self.save_mat = out.get("save_mat", False)
         self.save_ion_budget = bool(out.get("save_ion_budget", False))
+        self.save_fluxes = bool(out.get("save_fluxes", False))
         if "save_interval" in out:
             self.save_interval = out["save_interval"]
         self.out_file_prefix = problem.output_dir
@@ -389,7 +391,7 @@ class SolverKNPEMI:
         # traces, probe points, checkpoints (reference :96-99: init_png_savefile / init_checkpoint_file / init_data)
         from .output import RunOutput
         self.output = RunOutput(self) if (self.save_pngs or self.save_dat or self.save_cpoints or self.save_xdmfs or p.point_evaluation
-                                          or self.save_ion_budget) else None
+                                          or self.save_ion_budget or self.save_fluxes) else None
         if self.output is not None:
             self.output.record(0)
 
@@ -544,6 +546,8 @@ class SolverKNPEMI:
         self.print_info()
         if self.save_ion_budget and self.output is not None:
             self.output.save_ion_budget()
+        if self.save_fluxes and self.output is not None:
+            self.output.save_fluxes()
         if self.save_pngs and self.output is not None:
             self.output.figures()
         if self.save_dat:

@@ -1,7 +1,8 @@
-// Diagnostics (knp_diag_*): per-tag volume integrals of the ion fields and per-tag membrane integrals of one bytecode program.
+// Diagnostics (knp_diag_*): per-tag volume integrals of the ion fields, per-tag membrane integrals of one bytecode program and
+// per-tag trans-membrane ion fluxes.
 // Included at the end of knp_kernels.hip, after the host helpers (dev_upload, check_fields, validate_program) it uses.
 //
-// Both integrals reduce per tag without floating-point atomics.  The items (owned cells / selected membrane facets) are sorted by
+// All of them reduce per tag without floating-point atomics.  The items (owned cells / selected membrane facets) are sorted by
 // their dense tag index on the host, once; a block takes a fixed-size chunk of consecutive items, sums each run of equal tags inside
 // the chunk with a segmented scan in LDS and stores one partial per (chunk, tag) pair at index tag + chunk (unique: consecutive
 // chunks share at most their boundary tag).  A second pass adds a tag's partials in chunk order, one wave per tag.  The work split
@@ -134,6 +135,62 @@ __global__ void __launch_bounds__(DIAG_BT) k_diag_facets(int n, const int32_t* _
     diag_chunk_partials<1, DIAG_BT>(live ? key[i] : -1, live, i == n - 1, val, partial);
 }
 
+// (c) molar flux of every ion through the selected membrane facets, on both sides:
+//   flux[s][k] = -D_k (W0 sum_a g^s_a c^s_k(v^s_a) + (z_k/psi) (sum_b W_b c^s_k(f_b)) (sum_a g^s_a phi^s(v^s_a)))
+// with g^s_a = grad(lambda_a) . n_s on the side's cell (n_s: unit normal out of that cell), W0 = |F| sum_q w_q m_q and
+// W_b = |F| sum_q w_q m_q lambda_b(q) (m: the box mask at the quadrature points).  Everything but the nodal values is time invariant
+// and comes from one record per facet, built on the host (flux_records) in the order of the tag map.  The record, in 16-byte units:
+//   [0] 4 x int32 vertices of the intracellular cell: the facet's vertices f_0..f_{DIM-1} first, the opposite vertex at DIM
+//   [1] the same for the extracellular cell (same facet vertices, its own opposite vertex); in 2D the fourth id is unused
+//   then doubles g^0[DIM+1], g^1[DIM+1], W0, W_b[DIM] (2D: one pad) -- 128 B in 3D, 112 B in 2D.
+template <int DIM> struct FluxRecord { static constexpr int UNITS = DIM == 3 ? 8 : 7; };
+struct FluxCoef { double D[3], zp[3]; };
+template <int DIM>
+__global__ void __launch_bounds__(NT) k_diag_fluxes(int n, const int32_t* __restrict__ key, const double2* __restrict__ rec, FieldPtrs f,
+                                                    const double* __restrict__ phi_i, const double* __restrict__ phi_e, FluxCoef K,
+                                                    double* __restrict__ partial) {
+    constexpr int UNITS = FluxRecord<DIM>::UNITS, ND = 2 * (UNITS - 2);
+    const int i = blockIdx.x * NT + threadIdx.x;
+    const bool live = i < n;
+    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    int k = -1;
+    if (live) {
+        k = key[i];
+        const double2* r = rec + (size_t)i * UNITS;
+        const int4 ia = *reinterpret_cast<const int4*>(r), ib = *reinterpret_cast<const int4*>(r + 1);
+        const int vs[2][4] = {{ia.x, ia.y, ia.z, ia.w}, {ib.x, ib.y, ib.z, ib.w}};
+        double d[ND];
+#pragma unroll
+        for (int u = 0; u < UNITS - 2; ++u) {
+            const double2 t = r[2 + u];
+            d[2 * u] = t.x;
+            d[2 * u + 1] = t.y;
+        }
+        const double W0 = d[2 * (DIM + 1)];
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const double* g = d + s * (DIM + 1);
+            const double* ph = s ? phi_e : phi_i;
+            double gphi = 0.0;
+#pragma unroll
+            for (int a = 0; a <= DIM; ++a) gphi += g[a] * ph[vs[s][a]];
+#pragma unroll
+            for (int j = 0; j < 3; ++j) {
+                const double* c = s ? f.ke[j] : f.ki[j];
+                double gc = 0.0, wc = 0.0;
+#pragma unroll
+                for (int a = 0; a <= DIM; ++a) {
+                    const double ca = c[vs[s][a]];
+                    gc += g[a] * ca;
+                    if (a < DIM) wc += d[2 * (DIM + 1) + 1 + a] * ca;
+                }
+                v[3 * s + j] = -K.D[j] * (W0 * gc + K.zp[j] * wc * gphi);
+            }
+        }
+    }
+    diag_chunk_partials<6, NT>(k, live, i == n - 1, v, partial);
+}
+
 // a tag's partials in chunk order, one wave per tag; empty tags give zero
 template <int NV>
 __global__ void __launch_bounds__(NT) k_diag_combine(int n_tags, int chunk, const int32_t* __restrict__ seg_ptr,
@@ -165,6 +222,8 @@ static void diag_map_free(KnpDiagMap& m) {
 void knp_diag_free(knp_ctx* ctx) {
     diag_map_free(ctx->diag_cells);
     diag_map_free(ctx->diag_facets);
+    diag_map_free(ctx->diag_flux);
+    dev_free(ctx->d_flux_rec);
     dev_free(ctx->diag_code);
     ctx->diag_n_instr = ctx->diag_n_regs = ctx->diag_n_consts = 0;
     ctx->diag_prog = false;
@@ -207,11 +266,99 @@ static int diag_map_set(knp_ctx* ctx, KnpDiagMap& m, int n_tags, const int32_t* 
 static int diag_combine(knp_ctx* ctx, const KnpDiagMap& m, int nv, double* out) {
     if (m.n_tags == 0) return KNP_OK;
     const unsigned nb = (unsigned)((m.n_tags + NT / 64 - 1) / (NT / 64));
-    if (nv == 3)
+    if (nv == 6)
+        hipLaunchKernelGGL(k_diag_combine<6>, dim3(nb), dim3(NT), 0, ctx->stream, m.n_tags, m.chunk, m.d_ptr, m.d_partial, out);
+    else if (nv == 3)
         hipLaunchKernelGGL(k_diag_combine<3>, dim3(nb), dim3(NT), 0, ctx->stream, m.n_tags, m.chunk, m.d_ptr, m.d_partial, out);
     else
         hipLaunchKernelGGL(k_diag_combine<1>, dim3(nb), dim3(NT), 0, ctx->stream, m.n_tags, m.chunk, m.d_ptr, m.d_partial, out);
     HIPCHK(hipGetLastError());
+    return KNP_OK;
+}
+
+// gradients of the barycentric coordinates of the simplex x[0..DIM] (rows of DIM coordinates): G[a] = grad(lambda_a); false when flat
+template <int DIM>
+static bool simplex_gradients(const double (*x)[3], double (*G)[3]) {
+    double e[3][3] = {{0}};
+    for (int a = 0; a < DIM; ++a)
+        for (int c = 0; c < DIM; ++c) e[a][c] = x[a + 1][c] - x[0][c];
+    if (DIM == 2) {
+        const double det = e[0][0] * e[1][1] - e[0][1] * e[1][0];
+        if (det == 0.0) return false;
+        G[1][0] = e[1][1] / det;  G[1][1] = -e[1][0] / det;
+        G[2][0] = -e[0][1] / det; G[2][1] = e[0][0] / det;
+    } else {
+        double cr[3][3];      // cr[a] = e[a+1] x e[a+2]: grad(lambda_{a+1}) = cr[a] / det
+        for (int a = 0; a < 3; ++a) {
+            const double *u = e[(a + 1) % 3], *w = e[(a + 2) % 3];
+            cr[a][0] = u[1] * w[2] - u[2] * w[1]; cr[a][1] = u[2] * w[0] - u[0] * w[2]; cr[a][2] = u[0] * w[1] - u[1] * w[0];
+        }
+        const double det = e[0][0] * cr[0][0] + e[0][1] * cr[0][1] + e[0][2] * cr[0][2];
+        if (det == 0.0) return false;
+        for (int a = 0; a < 3; ++a)
+            for (int c = 0; c < 3; ++c) G[a + 1][c] = cr[a][c] / det;
+    }
+    for (int c = 0; c < DIM; ++c) {
+        G[0][c] = 0.0;
+        for (int a = 1; a <= DIM; ++a) G[0][c] -= G[a][c];
+    }
+    return true;
+}
+
+// the records of k_diag_fluxes for the facets of a tag map, in map order (host, once per map)
+template <int DIM>
+static int flux_records(knp_ctx* ctx, const int32_t* facets, int n, const std::vector<double>& coords, const double* q_pts,
+                        const double* q_w, const double* lo, const double* hi, std::vector<double2>& rec) {
+    constexpr int UNITS = FluxRecord<DIM>::UNITS;
+    const KnpHostGraph& g = ctx->g;
+    rec.assign((size_t)n * UNITS, make_double2(0.0, 0.0));
+    int64_t bad = 0;
+#pragma omp parallel for schedule(static) reduction(+ : bad) num_threads(knp_host_threads())
+    for (int i = 0; i < n; ++i) {
+        const int F = facets[i];
+        int32_t ids[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+        double d[2 * (UNITS - 2)] = {0.0};
+        double xf[DIM + 1][3], G[DIM + 1][3], nrm[3];
+        bool ok = g.gopp[(size_t)2 * F + 1] >= 0;
+        for (int s = 0; s < 2 && ok; ++s) {
+            for (int b = 0; b < DIM; ++b) ids[s][b] = g.fv[(size_t)F * DIM + b];
+            ids[s][DIM] = g.gopp[(size_t)2 * F + s];
+            for (int a = 0; a <= DIM; ++a)
+                for (int c = 0; c < DIM; ++c) xf[a][c] = coords[(size_t)ids[s][a] * DIM + c];
+            ok = simplex_gradients<DIM>(xf, G);
+            if (!ok) break;
+            if (s == 0) {     // grad(lambda_opposite) points into the cell along the facet normal: n_0 = -grad / |grad|, n_1 = -n_0
+                double len = 0.0;
+                for (int c = 0; c < DIM; ++c) len += G[DIM][c] * G[DIM][c];
+                len = std::sqrt(len);
+                for (int c = 0; c < DIM; ++c) nrm[c] = -G[DIM][c] / len;
+            }
+            for (int a = 0; a <= DIM; ++a) {
+                double t = 0.0;
+                for (int c = 0; c < DIM; ++c) t += G[a][c] * nrm[c];
+                d[s * (DIM + 1) + a] = s == 0 ? t : -t;
+            }
+        }
+        if (!ok) { ++bad; continue; }
+        double* W = d + 2 * (DIM + 1);     // W0, W_b: the facet rule with the mask at its points (side 1's xf holds the facet vertices first)
+        for (int q = 0; q < g.n_q; ++q) {
+            bool in = true;
+            if (lo)
+                for (int c = 0; c < DIM; ++c) {
+                    double x = 0.0;
+                    for (int b = 0; b < DIM; ++b) x += q_pts[(size_t)q * DIM + b] * xf[b][c];
+                    in = in && lo[c] < x && x < hi[c];
+                }
+            if (!in) continue;
+            const double w = g.fmeas[F] * q_w[q];
+            W[0] += w;
+            for (int b = 0; b < DIM; ++b) W[1 + b] += w * q_pts[(size_t)q * DIM + b];
+        }
+        double2* r = &rec[(size_t)i * UNITS];
+        std::memcpy(r, ids, sizeof(ids));
+        std::memcpy(r + 2, d, sizeof(d));
+    }
+    if (bad) { ctx->err = "flux facet map: a listed facet has a flat cell or an extracellular cell that does not hold the facet"; return KNP_E_MESH; }
     return KNP_OK;
 }
 
@@ -301,6 +448,60 @@ int knp_diag_membrane_integral(knp_ctx* ctx, const knp_fields* fields, double* o
         HIPCHK(hipGetLastError());
     }
     return diag_combine(ctx, m, 1, out);
+}
+
+int knp_diag_set_flux_facets(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr, const int32_t* facets, const double* box_lo,
+                             const double* box_hi) {
+    CHECK_CTX(ctx);
+    if ((box_lo == nullptr) != (box_hi == nullptr)) { ctx->err = "flux facet map: box_lo and box_hi must both be given or both be null"; return KNP_E_ARG; }
+    const KnpHostGraph& g = ctx->g;
+    KCHK(diag_map_set(ctx, ctx->diag_flux, n_tags, seg_ptr, facets, g.n_g, NT, 6, "flux facet map"));
+    dev_free(ctx->d_flux_rec);
+    const int n = ctx->diag_flux.n;
+    std::vector<double> coords((size_t)g.n_v * g.dim), qp((size_t)g.n_q * g.dim), qw((size_t)g.n_q);
+    std::vector<double2> rec;
+    int rc = KNP_OK;
+    if (hipMemcpy(coords.data(), ctx->d_coords, coords.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(qp.data(), ctx->d_qp, qp.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(qw.data(), ctx->d_qw, qw.size() * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) {
+        ctx->err = "flux facet map: reading the mesh back failed";
+        rc = KNP_E_HIP;
+    }
+    if (rc == KNP_OK)
+        rc = g.dim == 2 ? flux_records<2>(ctx, facets, n, coords, qp.data(), qw.data(), box_lo, box_hi, rec)
+                        : flux_records<3>(ctx, facets, n, coords, qp.data(), qw.data(), box_lo, box_hi, rec);
+    if (rc == KNP_OK) rc = dev_upload(ctx, &ctx->d_flux_rec, rec);
+    if (rc != KNP_OK) {     // no half-set map: the next knp_diag_membrane_fluxes reports KNP_E_STATE
+        diag_map_free(ctx->diag_flux);
+        dev_free(ctx->d_flux_rec);
+    }
+    return rc;
+}
+
+int knp_diag_membrane_fluxes(knp_ctx* ctx, const knp_fields* fields, const double* phi_i, const double* phi_e, const double* D,
+                             const double* z_over_psi, double* out) {
+    CHECK_CTX(ctx);
+    if (!fields) { ctx->err = "null fields"; return KNP_E_ARG; }
+    for (int j = 0; j < 3; ++j)
+        if (!fields->k_i[j] || !fields->k_e[j]) { ctx->err = "null concentration field"; return KNP_E_ARG; }
+    if (!phi_i || !phi_e) { ctx->err = "null potential field (phi_i / phi_e)"; return KNP_E_ARG; }
+    if (!D || !z_over_psi) { ctx->err = "null flux coefficients (D / z_over_psi)"; return KNP_E_ARG; }
+    if (!out) { ctx->err = "null output buffer"; return KNP_E_ARG; }
+    const KnpDiagMap& m = ctx->diag_flux;
+    if (!m.d_ptr || !ctx->d_flux_rec) { ctx->err = "no flux facet map (knp_diag_set_flux_facets)"; return KNP_E_STATE; }
+    if (m.n > 0) {
+        const FieldPtrs f = make_fields(fields);
+        FluxCoef K;
+        for (int j = 0; j < 3; ++j) { K.D[j] = D[j]; K.zp[j] = z_over_psi[j]; }
+        if (ctx->g.dim == 2)
+            hipLaunchKernelGGL(k_diag_fluxes<2>, dim3(m.n_chunks), dim3(NT), 0, ctx->stream, m.n, m.d_key, ctx->d_flux_rec, f, phi_i, phi_e, K,
+                               m.d_partial);
+        else
+            hipLaunchKernelGGL(k_diag_fluxes<3>, dim3(m.n_chunks), dim3(NT), 0, ctx->stream, m.n, m.d_key, ctx->d_flux_rec, f, phi_i, phi_e, K,
+                               m.d_partial);
+        HIPCHK(hipGetLastError());
+    }
+    return diag_combine(ctx, m, 6, out);
 }
 
 }  // extern "C"

@@ -35,6 +35,7 @@ struct KnpHostGraph {
     // membrane graph
     std::vector<int32_t> fv;                      // [n_g*dim] facet vertices
     std::vector<double> fmeas;                    // [n_g]
+    std::vector<int32_t> gopp;                    // [n_g*2] vertex of the intra / extra cell opposite the facet (-1: that cell does not hold the facet)
     int n_gv = 0;                                 // owned membrane vertices
     std::vector<int32_t> gv_vertex, gv_node_i, gv_node_e;  // [n_gv]
     std::vector<int32_t> node_gv;                 // [n_nodes_owned] index of the membrane vertex or -1
@@ -373,6 +374,9 @@ struct knp_ctx {
     size_t tm_used = 0;
     // diagnostics (knp_diag_*): per-tag ion amounts and membrane integrals of one program, outside the assembly's program table
     KnpDiagMap diag_cells, diag_facets;
+    // trans-membrane ion fluxes (knp_diag_set_flux_facets): a tag map of its own and one time-invariant record per listed facet, in map order
+    KnpDiagMap diag_flux;
+    double2* d_flux_rec = nullptr;   // [diag_flux.n * (dim == 3 ? 8 : 7)] 16-byte units, layout at k_diag_fluxes
     int32_t* diag_code = nullptr;
     int diag_n_instr = 0, diag_n_regs = 0, diag_n_consts = 0;
     double diag_consts[KNP_DIAG_MAX_CONSTS] = {};   // host copy: passed to the kernel by value at every launch

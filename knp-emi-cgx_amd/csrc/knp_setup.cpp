@@ -213,6 +213,7 @@ int knp_build_graph(const knp_mesh_desc* m, KnpHostGraph& g) {
     const int ng = g.n_g;
     g.fv.resize((size_t)ng * dim);
     g.fmeas.resize(ng);
+    g.gopp.assign((size_t)ng * 2, -1);
     for (int f = 0; f < ng; ++f) {
         int cp = m->gamma[4 * f], lp = m->gamma[4 * f + 1], cm = m->gamma[4 * f + 2];
         if (cp < 0 || cp >= g.n_c || cm < 0 || cm >= g.n_c || lp < 0 || lp >= nv1) { g.error = "gamma entry out of range"; return KNP_E_MESH; }
@@ -220,6 +221,15 @@ int knp_build_graph(const knp_mesh_desc* m, KnpHostGraph& g) {
         int k = 0;
         for (int a = 0; a < nv1; ++a)
             if (a != lp) g.fv[(size_t)f * dim + k++] = cells[(size_t)cp * nv1 + a];
+        g.gopp[(size_t)2 * f] = cells[(size_t)cp * nv1 + lp];
+        int n_off = 0, off = -1;             // the '-' cell's vertex off the facet, found by comparison (lf- is not trusted)
+        for (int a = 0; a < nv1; ++a) {
+            const int v = cells[(size_t)cm * nv1 + a];
+            bool on = false;
+            for (int b = 0; b < dim; ++b) on = on || g.fv[(size_t)f * dim + b] == v;
+            if (!on) { ++n_off; off = v; }
+        }
+        if (n_off == 1) g.gopp[(size_t)2 * f + 1] = off;
         const double* x0 = &m->coords[(size_t)g.fv[(size_t)f * dim] * dim];
         const double* x1 = &m->coords[(size_t)g.fv[(size_t)f * dim + 1] * dim];
         if (dim == 2) {

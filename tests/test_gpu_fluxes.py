@@ -1,0 +1,382 @@
+"""Trans-membrane ion fluxes per membrane tag on the device (k_diag_fluxes in csrc/knp_diagnostics.inc, cgx_hip/fluxes.py,
+``ProblemKNPEMI.membrane_fluxes``, output key ``save_fluxes``) against the independent NumPy evaluation of tests/flux_ref.py.
+
+Tolerance everywhere: |gpu - ref| <= 1e-12 * S with S the per-entry sum of magnitudes that flux_ref returns (about 4 500 ulp of the
+un-cancelled sum; the library's per-facet records are built by another formula than the checker's, and the gradient of a nearly
+constant concentration cancels, so the bound follows |c| |grad lambda| and not the result)."""
+import copy
+import ctypes as C
+import os
+import socket
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.multiprocessing as mp
+import yaml
+
+from flux_ref import TOL, coefficients, flux_ref, host_fields, region_box
+from parity_utils import ci_config, make_problem, tissue_config, two_cell_config, two_cell_mesh
+
+pytestmark = pytest.mark.gpu
+E_ARG, E_STATE = -1, -3          # KNP_E_ARG, KNP_E_STATE of include/knpemi_hip.h
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _close(got, ref, S):
+    err = np.abs(np.asarray(got) - np.asarray(ref))
+    print("max |gpu - ref| / S =", float(np.max(err / np.maximum(S, 1e-300))) if np.size(err) else 0.0)
+    return bool(np.all(err <= TOL * S))
+
+
+def _write(fn, values):
+    fn.x.array.copy_(torch.from_numpy(np.ascontiguousarray(values, dtype=np.float64)).to(fn.x.array.device))
+
+
+def _random_fields(p, seed):
+    rng = np.random.default_rng(seed)
+    n = p.local_mesh.coords.shape[0]
+    for s in range(2):
+        for j in range(p.N_ions):
+            _write(p.wh[s][j], rng.uniform(1.0, 150.0, n))
+        _write(p.wh[s][p.N_ions], rng.uniform(-0.1, 0.1, n))
+    _write(p.phi_m_prev, p.wh[0][p.N_ions].numpy() - p.wh[1][p.N_ions].numpy())
+
+
+def _reference(p, groups, mask):
+    D, zpsi = coefficients(p)
+    return flux_ref(p, host_fields(p), D, zpsi, groups, box=region_box(p) if mask else ())
+
+
+def _mesh_config(case):
+    if case == "square16":
+        return ci_config(N=16, steps=1)
+    if case == "cube8":
+        return ci_config(N=8, steps=1, kind="cube")
+    if case == "tissue2d":
+        return tissue_config(2, 18, 3, steps=1)
+    return tissue_config(3, 12, 2, steps=1)
+
+
+# ---- 1. random nodal fields ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["square16", "cube8", "tissue2d", "tissue3d"])
+def test_random_fields_match_the_reference_per_tag_side_and_ion(case):
+    p = make_problem(_mesh_config(case), "ci")
+    p.create_backend()
+    _random_fields(p, 11)
+    tags = [int(t) for t in p.gamma_tags]
+    out = p.membrane_fluxes()
+    ref, S, cover = _reference(p, [[t] for t in tags], False)
+    assert list(out["tag"]) == tags and out["flux_i"].shape == out["flux_e"].shape == (len(tags), 3)
+    if case == "tissue3d":
+        assert len(tags) == 8 and all(len(c) == 192 for c in cover)      # 1 536 facets in 6 blocks: tag boundaries inside blocks
+    assert np.all(S > 0) and np.all(np.abs(ref) > 0)
+    assert _close(out["flux_i"], ref[:, 0], S[:, 0]) and _close(out["flux_e"], ref[:, 1], S[:, 1])
+    lm = p.local_mesh
+    for t, tag in enumerate(tags):
+        assert out["area"][t] == pytest.approx(p._fmeas[np.asarray(lm.gamma_tags) == tag].sum(), rel=1e-13)
+    # a grouping that merges two tags into one slot, with an empty group in the middle (backend level: groups are lists of tags)
+    be = p.backend
+    groups = [tags[:2], [987654], tags[2:]] if len(tags) >= 3 else [tags + [987654], [987654]]
+    be.set_flux_groups(groups)
+    got = be.membrane_fluxes().cpu().numpy()
+    ref, S, cover = _reference(p, groups, False)
+    assert got.shape == (len(groups), 2, 3) and len(cover[1]) == 0
+    assert np.all(got[1] == 0.0) and np.all(ref[1] == 0.0)
+    assert _close(got, ref, S)
+    # the same bits on every run
+    assert be.membrane_fluxes().cpu().numpy().tobytes() == got.tobytes()
+
+
+# ---- 2. affine fields: the divergence theorem per closed cell membrane, volumes from the budget kernel --------------------------
+@pytest.mark.parametrize("dim,N,m", [(2, 18, 3), (3, 12, 2)])
+def test_affine_fields_give_the_cell_volume_times_the_mixed_term(dim, N, m):
+    p = make_problem(tissue_config(dim, N, m, steps=1), "ci")
+    p.create_backend()
+    x = p.local_mesh.coords
+    n = x.shape[0]
+    rng = np.random.default_rng(3)
+    g = [rng.uniform(0.5, 2.0, dim) * 2e7 for _ in range(3)]
+    h = rng.uniform(0.5, 2.0, dim) * 3e4
+    D, zpsi = coefficients(p)
+    tags = [int(t) for t in p.gamma_tags]
+    bud = p.ion_budget()
+    V = np.array([bud["volume"][list(bud["tag"]).index(t)] for t in tags])
+    assert np.all(V > 0)
+
+    def fluxes(cs, ph):
+        for s in range(2):
+            for j in range(3):
+                _write(p.wh[s][j], cs[j])
+            _write(p.wh[s][3], ph)
+        out = p.membrane_fluxes()
+        _, S, _ = _reference(p, [[t] for t in tags], False)
+        return out, S
+    # pure diffusion (phi = 0) and pure drift (constant concentrations): nothing leaves a closed surface
+    for cs, ph in (([30.0 + x @ gj for gj in g], np.zeros(n)), ([np.full(n, 12.0), np.full(n, 130.0), np.full(n, 5.0)], x @ h)):
+        out, S = fluxes(cs, ph)
+        assert np.all(S > 0)
+        assert np.all(np.abs(out["flux_i"]) <= TOL * S[:, 0]) and np.all(np.abs(out["flux_e"]) <= TOL * S[:, 1])
+    # both: -D_k (z_k/psi) (g_k.h) V_tag out of the cell, the opposite out of the extracellular space
+    out, S = fluxes([x @ gj for gj in g], x @ h)
+    for k in range(3):
+        want = -D[k] * zpsi[k] * float(g[k] @ h) * V
+        assert np.all(np.abs(want) > 1e3 * TOL * S[:, 0, k]), "the expected value drowns in the bound"
+        assert np.all(np.abs(out["flux_i"][:, k] - want) <= TOL * S[:, 0, k])
+        assert np.all(np.abs(out["flux_e"][:, k] + want) <= TOL * S[:, 1, k])
+
+
+# ---- 3. the stimulus-region mask ----------------------------------------------------------------------------------------------
+def _two_cell_cfg(tmp_path, steps=2):
+    coords, cells, tags, fverts, ftags = two_cell_mesh(16)
+    path = str(tmp_path / "twocells.npz")
+    np.savez(path, coords=coords, cells=cells, cell_tags=tags, facets=fverts, facet_tags=ftags)
+    return two_cell_config(path, steps=steps)
+
+
+@pytest.mark.parametrize("case", ["two_cell", "tissue3d_two_axes"])
+def test_mask_cuts_facets_at_the_quadrature_points(case, tmp_path):
+    if case == "two_cell":
+        from cgx_hip.configs import default_ionic_models
+        p = make_problem(_two_cell_cfg(tmp_path), default_ionic_models)
+        assert region_box(p) == [(1, pytest.approx(0.3e-6), pytest.approx(0.6e-6))]
+    else:
+        cfg = tissue_config(3, 12, 2, steps=1)
+        cfg["stimulus_region"] = {"multiple": True, "direction": ["x", "z"], "range": [[0.0, 0.3], [0.1, 0.8]]}
+        p = make_problem(cfg, "ci")
+    p.create_backend()
+    _random_fields(p, 23)
+    tags = [int(t) for t in p.gamma_tags]
+    ref, S, cover = _reference(p, [[t] for t in tags], True)
+    allc = np.concatenate(cover)
+    assert ((allc > 1e-12) & (allc < 1 - 1e-12)).any(), "no selected facet is partially covered"
+    assert (allc == 0).any(), "no selected facet is fully outside"
+    out = p.membrane_fluxes(mask=True)
+    assert _close(out["flux_i"], ref[:, 0], S[:, 0]) and _close(out["flux_e"], ref[:, 1], S[:, 1])
+    full, _, _ = _reference(p, [[t] for t in tags], False)
+    assert np.abs(full - ref).max() > 1e3 * TOL * S.max()     # the mask matters
+    # switching the mask off again rebuilds the records
+    out = p.membrane_fluxes(mask=False)
+    _, Sf, _ = _reference(p, [[t] for t in tags], False)
+    assert _close(out["flux_i"], full[:, 0], Sf[:, 0]) and _close(out["flux_e"], full[:, 1], Sf[:, 1])
+
+
+# ---- 4. after real steps ------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", ["square16", "tissue2d"])
+def test_compute_fluxes_after_real_steps(case):
+    from CGx.KNPEMI.KNPEMIx_solver import SolverKNPEMI
+    from CGx.utils.calc_fluxes import compute_fluxes, create_flux_forms
+    cfg = ci_config(N=16, steps=3, rtol=1e-11) if case == "square16" else tissue_config(2, 18, 3, steps=3, rtol=1e-11, stimulus=True)
+    p = make_problem(cfg, "ci")
+    p.solver_config["view_ksp"] = False
+    s = SolverKNPEMI(p, solver_config=p.solver_config)
+    s.solve()
+    forms = create_flux_forms(p)
+    got = compute_fluxes(forms, p.comm)
+    assert got.shape == (6,)
+    ref, S, cover = _reference(p, [[int(p.membrane_data_tag)]], True)
+    assert len(cover[0]) > 0 and np.all(np.abs(ref) > 0)
+    assert _close(got, ref.reshape(-1), S.reshape(-1))
+    out = p.membrane_fluxes(tags=[p.membrane_data_tag], mask=True)
+    assert np.array_equal(np.concatenate([out["flux_i"][0], out["flux_e"][0]]), got)
+    assert np.array_equal(compute_fluxes(forms[::-1], p.comm), got[::-1])
+
+
+# ---- 5. CGx.KNPEMI.main with save_fluxes --------------------------------------------------------------------------------------
+def _write_cfg(tmp_path, name, cfg, out_dir, save_fluxes):
+    cfg = copy.deepcopy(cfg)
+    cfg["output_dir"] = str(out_dir) + "/"
+    cfg["solver"]["output"].update({"save_pngs": True, "save_dat": True})
+    if save_fluxes:
+        cfg["solver"]["output"]["save_fluxes"] = True
+    path = tmp_path / name
+    with open(path, "w") as f:
+        yaml.safe_dump(cfg, f)
+    return str(path)
+
+
+def _run_main_with_host_fluxes(path):
+    """CGx.KNPEMI.main --config, evaluating at every record the reference with that step's fields"""
+    from cgx_hip import output as outmod
+    from CGx.KNPEMI import main as mainmod
+    host = []
+    orig = outmod.RunOutput.record
+
+    def record(self, i):
+        orig(self, i)
+        ref, S, _ = _reference(self.p, [[int(self.p.membrane_data_tag)]], True)
+        host.append((ref.reshape(-1), S.reshape(-1)))
+    outmod.RunOutput.record = record
+    try:
+        s = mainmod.main(["--config", path])
+    finally:
+        outmod.RunOutput.record = orig
+    return s, np.array([h[0] for h in host]), np.array([h[1] for h in host])
+
+
+def test_main_writes_the_flux_trace(tmp_path):
+    steps = 4
+    cfg = tissue_config(2, 18, 3, steps=steps, rtol=1e-11)
+    s, ref, S = _run_main_with_host_fluxes(_write_cfg(tmp_path, "flux_a.yml", cfg, tmp_path / "a", True))
+    a = np.load(tmp_path / "a" / "fluxes.npy")
+    assert a.shape == ref.shape == (steps + 1, 6)
+    assert _close(a, ref, S)
+    assert np.abs(a[-1] - a[0]).max() > 0                     # the steps moved the fields
+    from CGx.KNPEMI import main as mainmod
+    mainmod.main(["--config", _write_cfg(tmp_path, "flux_b.yml", cfg, tmp_path / "b", True)])
+    with open(tmp_path / "a" / "fluxes.npy", "rb") as fa, open(tmp_path / "b" / "fluxes.npy", "rb") as fb:
+        assert fa.read() == fb.read()
+    cfg1 = tissue_config(2, 18, 3, steps=1, rtol=1e-11)
+    s = mainmod.main(["--config", _write_cfg(tmp_path, "flux_c.yml", cfg1, tmp_path / "c", False)])
+    assert (tmp_path / "c" / "stimulus.npy").exists() and not (tmp_path / "c" / "fluxes.npy").exists()
+    assert s.output.fluxes is None and getattr(s.backend, "_flux_key", None) is None      # nothing allocated, nothing set
+
+
+# ---- 6. two ranks on one GPU against one rank ---------------------------------------------------------------------------------
+def _free_port():
+    sk = socket.socket()
+    sk.bind(("127.0.0.1", 0))
+    port = sk.getsockname()[1]
+    sk.close()
+    return port
+
+
+def _worker(rank, size, port, out_dir, q):
+    try:
+        for path in (os.path.join(ROOT, "knp-emi-cgx_amd"), os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")):
+            sys.path.insert(0, path)
+        os.environ["MASTER_ADDR"] = "127.0.0.1"
+        os.environ["MASTER_PORT"] = str(port)
+        import torch.distributed as dist
+        torch.cuda.set_device(0)
+        if size > 1:
+            dist.init_process_group("gloo", rank=rank, world_size=size)
+        from parity_utils import run_native
+        from cgx_hip import output as outmod
+        host = []
+        orig = outmod.RunOutput.record
+
+        def sum_ranks(p, a):
+            return np.sum(p.comm.all_gather_object(a), axis=0) if p.comm.size > 1 else a
+
+        def record(self, i):                # the reference on this rank layout's own fields, summed over the ranks
+            orig(self, i)
+            ref, S, _ = _reference(self.p, [[int(self.p.membrane_data_tag)]], True)
+            host.append((sum_ranks(self.p, ref.reshape(-1)), sum_ranks(self.p, S.reshape(-1))))
+        outmod.RunOutput.record = record
+        cfg = tissue_config(2, 18, 3, steps=3, rtol=1e-13)
+        cfg["output_dir"] = out_dir + "/"
+        cfg["solver"]["output"].update({"save_dat": True, "save_fluxes": True})
+        s = run_native(cfg)
+        p = s.problem
+        tags = [int(t) for t in p.gamma_tags]
+        out = p.membrane_fluxes()
+        ref, S, _ = _reference(p, [[t] for t in tags], False)
+        q.put((rank, "ok", {k: np.asarray(v) for k, v in out.items()}, sum_ranks(p, ref), sum_ranks(p, S),
+               np.array([h[0] for h in host]), np.array([h[1] for h in host])))
+        if size > 1:
+            dist.barrier()
+            dist.destroy_process_group()
+    except Exception:      # noqa: BLE001
+        import traceback
+        q.put((rank, traceback.format_exc(), None, None, None, None, None))
+
+
+def _spawn(layouts):
+    """one group of worker processes per (size, out_dir), all groups at once (three processes on the GPU)"""
+    ctx = mp.get_context("spawn")
+    groups = []
+    for size, out_dir in layouts:
+        q = ctx.Queue()
+        port = _free_port()
+        procs = [ctx.Process(target=_worker, args=(r, size, port, out_dir, q)) for r in range(size)]
+        for pr in procs:
+            pr.start()
+        groups.append((size, q, procs))
+    out = []
+    for size, q, procs in groups:
+        res = sorted([q.get(timeout=300) for _ in range(size)], key=lambda r: r[0])
+        for pr in procs:
+            pr.join(timeout=60)
+        for r in res:
+            assert r[1] == "ok", f"rank {r[0]}:\n{r[1]}"
+        out.append(res)
+    return out
+
+
+def test_two_ranks_give_the_one_rank_fluxes(tmp_path):
+    """On each layout the results equal the reference on that layout's own fields.  Across layouts the fields are the same at
+    record 0 (1e-12 S); later records follow the two solves' trajectories, held to the 1e-6 that
+    test_two_ranks_give_the_one_rank_budgets takes from the multi-rank solve tests for its stimulus trace -- here of S, the
+    un-cancelled sum the flux's rounding scales with."""
+    (one,), two = _spawn([(1, str(tmp_path / "one")), (2, str(tmp_path / "two"))])
+    a, b = np.load(tmp_path / "one" / "fluxes.npy"), np.load(tmp_path / "two" / "fluxes.npy")
+    assert a.shape == b.shape == (4, 6)
+    for trace, res in ((a, one), (b, two[0])):
+        assert _close(trace, res[5], res[6])
+    for r in [one] + two:                  # every rank returns the sums over ranks: all membrane tags, no mask, final state
+        flux = np.stack([r[2]["flux_i"], r[2]["flux_e"]], axis=1)
+        assert flux.shape == r[3].shape == (9, 2, 3)
+        assert _close(flux, r[3], r[4])
+    assert np.allclose(two[0][2]["area"], one[2]["area"], rtol=1e-12, atol=0) and np.array_equal(two[0][2]["tag"], one[2]["tag"])
+    assert np.all(np.abs(b[0] - a[0]) <= TOL * one[6][0])
+    assert np.all(np.abs(b - a) <= 1e-6 * one[6])
+    f1 = np.stack([one[2]["flux_i"], one[2]["flux_e"]], axis=1)
+    f2 = np.stack([two[0][2]["flux_i"], two[0][2]["flux_e"]], axis=1)
+    assert np.all(np.abs(f2 - f1) <= 1e-6 * one[4])
+
+
+# ---- 7. the C ABI -------------------------------------------------------------------------------------------------------------
+def test_abi_states_arguments_and_map_replacement():
+    from cgx_hip.backend import _f64, _i32
+    p = make_problem(tissue_config(3, 12, 2, steps=1), "ci")
+    be = p.create_backend()
+    lib, ctx = be.lib, be.ctx
+    _random_fields(p, 31)
+    n_g = p.local_mesh.gamma.shape[0]
+    D, zpsi = coefficients(p)
+    f = be.fields()
+    phi_i, phi_e = C.c_void_p(p.wh[0][3].data_ptr()), C.c_void_p(p.wh[1][3].data_ptr())
+    out = torch.zeros(6, dtype=torch.float64, device=be.device)
+    outp = C.c_void_p(out.data_ptr())
+    err = lambda: lib.knp_last_error(ctx).decode()
+    # before a map
+    assert lib.knp_diag_membrane_fluxes(ctx, C.byref(f), phi_i, phi_e, _f64(D), _f64(zpsi), outp) == E_STATE
+    assert "no flux facet map" in err()
+    # bad maps: an index past the mesh's facets, a facet listed twice, a mask with one corner
+    ptr = np.array([0, 2], dtype=np.int32)
+    assert lib.knp_diag_set_flux_facets(ctx, 1, _i32(ptr), _i32(np.array([0, n_g], dtype=np.int32)), None, None) == E_ARG
+    assert "out of range or listed twice" in err()
+    assert lib.knp_diag_set_flux_facets(ctx, 1, _i32(ptr), _i32(np.array([5, 5], dtype=np.int32)), None, None) == E_ARG
+    assert "out of range or listed twice" in err()
+    lo = np.zeros(3)
+    assert lib.knp_diag_set_flux_facets(ctx, 1, _i32(ptr), _i32(np.array([0, 1], dtype=np.int32)), _f64(lo), None) == E_ARG
+    assert "box_lo and box_hi" in err()
+    assert lib.knp_diag_membrane_fluxes(ctx, C.byref(f), phi_i, phi_e, _f64(D), _f64(zpsi), outp) == E_STATE
+    # a map, then null arguments
+    assert lib.knp_diag_set_flux_facets(ctx, 1, _i32(ptr), _i32(np.array([0, 1], dtype=np.int32)), None, None) == 0
+    assert lib.knp_diag_membrane_fluxes(ctx, C.byref(f), phi_i, phi_e, _f64(D), _f64(zpsi), None) == E_ARG
+    assert "null output" in err()
+    assert lib.knp_diag_membrane_fluxes(ctx, C.byref(f), None, phi_e, _f64(D), _f64(zpsi), outp) == E_ARG
+    assert "null potential" in err()
+    assert lib.knp_diag_membrane_fluxes(ctx, None, phi_i, phi_e, _f64(D), _f64(zpsi), outp) == E_ARG
+    assert lib.knp_diag_membrane_fluxes(ctx, C.byref(f), phi_i, phi_e, None, _f64(zpsi), outp) == E_ARG
+    assert lib.knp_diag_membrane_fluxes(ctx, C.byref(f), phi_i, phi_e, _f64(D), _f64(zpsi), outp) == 0
+    # a second map replaces the first: results follow the new map, and setting maps over and over does not grow the device's use
+    tags = [int(t) for t in p.gamma_tags]
+    be.set_flux_groups([tags])
+    torch.cuda.synchronize()
+    free0 = torch.cuda.mem_get_info()[0]
+    for k in range(100):
+        be.set_flux_groups([tags[:1 + k % 2]])
+        be.set_flux_groups([[t] for t in tags])
+    got = be.membrane_fluxes().cpu().numpy()
+    free1 = torch.cuda.mem_get_info()[0]
+    ref, S, _ = _reference(p, [[t] for t in tags], False)
+    assert _close(got, ref, S)
+    # one map of 1 536 facets holds about 0.25 MB; 200 leaked ones would be 50 MB
+    assert free0 - free1 < 8 * 2 ** 20, (free0, free1)
+    # the stimulus trace's facet map lives next to it
+    be.set_facet_groups([tags])
+    assert be.membrane_fluxes().cpu().numpy().tobytes() == got.tobytes()
