@@ -35,6 +35,9 @@
  *        assemble_scalar(stim_ufl_expr*dS(stimulus_tags)) of the stimulus trace (KNPEMIx_solver.py:580-582, 605-607)
  *   knp_diag_set_flux_facets / knp_diag_membrane_fluxes
  *        assemble_scalar of the six forms of create_flux_forms (utils/calc_fluxes.py:70-90), per membrane tag
+ *   knp_diag_set_phim_facets / knp_diag_membrane_potential
+ *        integral, minimum and maximum of phi_m per membrane tag: what utils/plot_membrane_potentials.py:48-128 reads per cell from
+ *        the reference's per-step checkpoints
  *   knp_set_comm                     the MPI calls hidden in PETSc/DOLFINx (ghost updates
  *                                    KNPEMIx_solver.py:439,459,468; Allreduce inside KSPSolve)
  *
@@ -390,6 +393,18 @@ int knp_diag_set_flux_facets(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_pt
 int knp_diag_membrane_fluxes(knp_ctx* ctx, const knp_fields* fields, const double* phi_i /* device [n_vertices] */,
                              const double* phi_e /* device [n_vertices] */, const double* D /* host [3] */,
                              const double* z_over_psi /* host [3] */, double* out /* device [n_tags*6] */);
+/* knp_diag_set_phim_facets: a tag map of membrane facets like knp_diag_set_facet_tags, kept apart from it and from the flux map (all
+ *   three may be live); validated and replaced by the same rules.  Synchronous.
+ * knp_diag_membrane_potential: with phi = fields->phi_m (nodal; the other fields are not read) and d the number of facet vertices,
+ *   out[3t] = sum over the facets F of tag t of |F|/d * sum_a phi(v_a(F)) (the exact P1 integral, V m^(d-1)), out[3t + 1] / out[3t + 2] =
+ *   the minimum / maximum of phi over all vertices of the tag's facets.  A tag without facets gives (0, +inf, -inf): the caller reduces
+ *   over ranks by sum / min / max and divides by the tag's area for the mean.  A NaN at a vertex of a tag's facets makes that
+ *   tag's integral NaN but not its minimum and maximum (fmin / fmax drop it): test out[3t] to detect a diverged field.  Partials are combined in a fixed order (one wave per tag
+ *   of at most 64 chunks of 128 facets, one workgroup per longer tag): the same bits on every run.  KNP_E_STATE before a map is set,
+ *   KNP_E_ARG for a null argument; n_tags == 0 is a successful no-op. */
+int knp_diag_set_phim_facets(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr /* host [n_tags+1] */,
+                             const int32_t* facets /* host [seg_ptr[n_tags]] */);
+int knp_diag_membrane_potential(knp_ctx* ctx, const knp_fields* fields, double* out /* device [n_tags*3] */);
 
 /* ---- instrumentation ---- */
 /* elapsed ms and launch count of a kernel class since the last reset (HIP events on the ctx stream).

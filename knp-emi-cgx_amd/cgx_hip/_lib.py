@@ -126,6 +126,8 @@ SIGNATURES = {
     "knp_diag_membrane_integral": (C.c_int, [vp, C.POINTER(Fields), vp]),
     "knp_diag_set_flux_facets": (C.c_int, [vp, C.c_int32, i32p, i32p, f64p, f64p]),
     "knp_diag_membrane_fluxes": (C.c_int, [vp, C.POINTER(Fields), vp, vp, f64p, f64p, vp]),
+    "knp_diag_set_phim_facets": (C.c_int, [vp, C.c_int32, i32p, i32p]),
+    "knp_diag_membrane_potential": (C.c_int, [vp, C.POINTER(Fields), vp]),
     "knp_timer_mark": (C.c_int, [vp, C.c_int32]),
     "knp_timer_read": (C.c_int, [vp, C.c_int32, f64p, C.POINTER(C.c_int32)]),
     "knp_timer_pending": (C.c_int, [vp]),

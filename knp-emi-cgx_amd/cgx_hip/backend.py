@@ -608,6 +608,37 @@ class Backend:
                                                      C.c_void_p(p.wh[1][p.N_ions].data_ptr()), _f64(D), _f64(zp), C.c_void_p(out.data_ptr())))
         return out
 
+    def set_phim_groups(self, groups):
+        """Membrane facets of this rank (owner of the first vertex) whose membrane tag is in ``groups[t]``, reduced into slot t of
+        ``membrane_potential`` (knp_diag_set_phim_facets); a call with the groups already set does nothing.  The map is apart from
+        the ones of ``set_facet_groups`` and ``set_flux_groups``."""
+        from .diagnostics import PhimLayout
+        groups = tuple(tuple(int(t) for t in g) for g in groups)
+        if getattr(self, "_phim", None) is not None and self._phim.groups == groups:
+            return
+        lay = PhimLayout(self.p, groups)
+        self._phim = None
+        self.check(self.lib.knp_diag_set_phim_facets(self.ctx, len(groups), _i32(lay.seg_ptr), _i32(lay.facets) if lay.facets.size else None))
+        self._phim = lay
+
+    def phim_layout(self):
+        """the groups of ``set_phim_groups`` (``tags``: each group's first tag) and this rank's area of each, built once per map"""
+        if getattr(self, "_phim", None) is None:
+            raise KnpError("phim_layout() before set_phim_groups()")
+        return self._phim
+
+    def membrane_potential(self, out=None):
+        """This rank's (integral of phi_m [V m^(d-1)], minimum, maximum [V]) over each facet group, [n_groups, 3] on the device:
+        enqueued, not waited for; a group without facets here gives (0, +inf, -inf).  ``out``: a contiguous float64 device tensor
+        of that size (a row of a preallocated trace), else a new one."""
+        lay = self.phim_layout()
+        if out is None:
+            out = torch.empty((lay.n_groups, 3), dtype=torch.float64, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.float64 and out.numel() == 3 * lay.n_groups
+        f = self.fields()
+        self.check(self.lib.knp_diag_membrane_potential(self.ctx, C.byref(f), C.c_void_p(out.data_ptr())))
+        return out
+
     # ---- exports (parity hooks) ------------------------------------------------------------
     def csr(self):
         """A as scipy CSR (rows = owned DoFs, cols = local DoFs), columns sorted."""

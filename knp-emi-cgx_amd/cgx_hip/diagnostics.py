@@ -1,6 +1,7 @@
 """Per-tag diagnostics of a run: ion amounts, charge, volume and membrane area per cell tag (reference
-KNPEMIx_problem.py:807-843, ``print_conservation``), the stimulus-current trace (KNPEMIx_solver.py:578-585, 604-610, 855-857) and the
-trans-membrane ion fluxes per membrane tag (utils/calc_fluxes.py; KNPEMIx_solver.py:626-627, 641-643).
+KNPEMIx_problem.py:807-843, ``print_conservation``), the stimulus-current trace (KNPEMIx_solver.py:578-585, 604-610, 855-857), the
+trans-membrane ion fluxes per membrane tag (utils/calc_fluxes.py; KNPEMIx_solver.py:626-627, 641-643) and the membrane potential
+per membrane tag (what utils/plot_membrane_potentials.py:48-128 reads per cell from the reference's checkpoints).
 
 The tag maps and the time-invariant measures are built here, on the host, once; the integrals of the fields are HIP kernels
 (csrc/knp_diagnostics.inc, ``knp_diag_*``) that run on the library's stream and write device buffers.  Reading a result is the
@@ -59,9 +60,17 @@ def facet_group_map(problem, groups):
     p = problem
     own = np.nonzero(owned_facets(p))[0]
     ftags = np.asarray(p.gamma_facet_tags)[own]
+    first = {}                                # membrane tag -> the first group that lists it (one pass: a group per cell is usual)
+    for t, tags in enumerate(groups):
+        for tag in tags:
+            first.setdefault(int(tag), t)
+    keys = np.array(sorted(first), dtype=np.int64)
+    vals = np.array([first[k] for k in keys], dtype=np.int64)
     group_of = np.full(len(own), -1, dtype=np.int64)
-    for t, tags in reversed(list(enumerate(groups))):
-        group_of[np.isin(ftags, list(tags))] = t
+    if len(keys) and len(own):
+        pos = np.minimum(np.searchsorted(keys, ftags), len(keys) - 1)
+        hit = keys[pos] == ftags
+        group_of[hit] = vals[pos[hit]]
     seg_ptr, items = tag_map(group_of, np.arange(len(groups)))
     return seg_ptr, np.ascontiguousarray(own[items], dtype=np.int32)
 
@@ -95,6 +104,60 @@ def facet_areas(problem, seg_ptr, facets):
     """area of every segment of a facet map (this rank's part)"""
     dense = np.repeat(np.arange(len(seg_ptr) - 1), np.diff(seg_ptr))
     return np.bincount(dense, weights=problem._fmeas[facets], minlength=len(seg_ptr) - 1).astype(np.float64)
+
+
+class PhimLayout:
+    """The facet groups of the membrane-potential reduction on this rank: ``groups`` (tuples of membrane tags), ``tags`` (each
+    group's first tag), the facet map (``facet_group_map``) and ``area``, this rank's part of A_t = sum_F |F| per group."""
+
+    def __init__(self, problem, groups):
+        self.groups = tuple(tuple(int(t) for t in g) for g in groups)
+        self.tags = np.array([g[0] if g else -1 for g in self.groups], dtype=np.int64)
+        self.seg_ptr, self.facets = facet_group_map(problem, self.groups)
+        self.area = facet_areas(problem, self.seg_ptr, self.facets)
+
+    @property
+    def n_groups(self):
+        return len(self.groups)
+
+
+def reduce_membrane_potential(parts, areas):
+    """Per-rank device results ``parts`` ([n, 3] = integral, min, max each; [..., n, 3] for traces) and per-rank ``areas`` [n],
+    reduced in rank order by sum / min / max: returns the area [n] and (mean, min, max) in the shape of one part.  A group without
+    a facet on any rank has area 0 and NaN for all three."""
+    area = np.sum(areas, axis=0)
+    I = np.sum([q[..., 0] for q in parts], axis=0)
+    lo = np.min([q[..., 1] for q in parts], axis=0)
+    hi = np.max([q[..., 2] for q in parts], axis=0)
+    none = area == 0.0
+    with np.errstate(divide="ignore", invalid="ignore"):
+        mean = np.where(none, np.nan, I / area)
+    return area, np.stack([mean, np.where(none, np.nan, lo), np.where(none, np.nan, hi)], axis=-1)
+
+
+def threshold_crossings(trace, times, threshold):
+    """Upward crossings of ``threshold`` per column of ``trace`` [records, n] sampled at ``times`` [records]: a crossing lies
+    between records i and i + 1 when trace[i] < threshold <= trace[i + 1].  Returns ``count`` [n] (int64) and ``first`` [n], the
+    linearly interpolated time of the first one (the sample's own time when it equals the threshold), NaN where there is none.
+    Applied to ``phi_m_tags.npy[:, :, 0]`` it gives the activation time of every cell."""
+    v = np.asarray(trace, dtype=np.float64)
+    t = np.asarray(times, dtype=np.float64)
+    if v.ndim == 1:
+        v = v[:, None]
+    if v.ndim != 2 or t.shape != (v.shape[0],):
+        raise ValueError("trace must be [records, n] and times [records]")
+    n = v.shape[1]
+    count = np.zeros(n, dtype=np.int64)
+    first = np.full(n, np.nan)
+    if v.shape[0] < 2:
+        return count, first
+    up = (v[:-1] < threshold) & (v[1:] >= threshold)
+    count = up.sum(axis=0).astype(np.int64)
+    cols = np.nonzero(count > 0)[0]
+    i = np.argmax(up[:, cols], axis=0)
+    a, b = v[i, cols], v[i + 1, cols]
+    first[cols] = t[i] + (threshold - a) / (b - a) * (t[i + 1] - t[i])
+    return count, first
 
 
 class BudgetLayout:

@@ -9,6 +9,7 @@ Mirrors reference
   src/CGx/KNPEMI/KNPEMIx_solver.py:799-821      checkpoints of the 2(N+1) solution functions every ``save_interval`` steps
   src/CGx/KNPEMI/KNPEMIx_solver.py:833-866      export_data: file names of the ``.npy`` artefacts
   src/CGx/KNPEMI/KNPEMIx_solver.py:578-610      stimulus current integrated over the stimulus membranes at every record (stimulus.npy)
+  utils/plot_membrane_potentials.py:48-128      phi_m, n, m, h of chosen cells at each cell's membrane vertex closest to the mesh centre
 The reference evaluates with scifem.evaluate_function (P1 interpolation in the cell containing the point) and checkpoints with
 adios4dolfinx; here the interpolation weights are found once on the host and each evaluation is one tiny device gather, and a
 checkpoint is an ``.npz`` of the nodal arrays per rank (with the local-to-global vertex map).
@@ -131,6 +132,60 @@ def find_membrane_measurement_vertex(problem):
             p.gamma_points = p.png_point
 
 
+def find_membrane_probe_vertices(problem, tags):
+    """For every membrane tag in ``tags`` the owned vertex of that tag's facets closest to the centre of the mesh's bounding box,
+    by the rule of ``find_membrane_measurement_vertex`` (smallest distance, then lowest rank; on a rank the lowest vertex index):
+    for ``membrane_data_tag`` it is that function's ``png_dof`` and owner (not in an MMS test, where that function searches the
+    facets of all ``gamma_tags`` at once).  Returns ``owner`` [n] (rank, -1 when no facet carries
+    the tag), ``vertex`` [n] (local index on the owner) and ``xyz`` [n, dim] in metres (NaN without a vertex).  One gather."""
+    p = problem
+    lm = p.local_mesh
+    mm = p.get_min_and_max_coordinates()
+    d = lm.coords.shape[1]
+    centre = np.array([(mm[2 * a] + mm[2 * a + 1]) / 2 for a in range(d)])
+    ftags = np.asarray(p.gamma_facet_tags, dtype=np.int64)
+    order = np.argsort(ftags, kind="stable")      # facets by tag, once: a tissue mesh has thousands of tags
+    want = np.asarray([int(t) for t in tags], dtype=np.int64)
+    lo, hi = np.searchsorted(ftags[order], want, side="left"), np.searchsorted(ftags[order], want, side="right")
+    mine = []
+    for t in range(len(want)):
+        gv = np.unique(p._fv[order[lo[t]:hi[t]]]) if hi[t] > lo[t] else np.zeros(0, dtype=np.int64)
+        gv = gv[gv < lm.n_vertices_owned]
+        if gv.size:
+            dist = ((lm.coords[gv] - centre) ** 2).sum(axis=1)
+            k = int(np.argmin(dist))
+            mine.append((float(dist[k]), p.comm.rank, int(gv[k]), lm.coords[gv[k]].tolist()))
+        else:
+            mine.append((np.inf, p.comm.rank, -1, None))
+    parts = p.comm.all_gather_object(mine)
+    n = len(mine)
+    owner, vertex, xyz = np.full(n, -1, dtype=np.int64), np.full(n, -1, dtype=np.int64), np.full((n, d), np.nan)
+    for t in range(n):
+        best = min((q[t] for q in parts), key=lambda c: (c[0], c[1]))
+        if best[2] >= 0:
+            owner[t], vertex[t], xyz[t] = best[1], best[2], best[3]
+    return {"owner": owner, "vertex": vertex, "xyz": xyz}
+
+
+def parse_membrane_potential_keys(out_cfg, gamma_tags):
+    """``save_membrane_potentials`` / ``membrane_potential_interval`` of ``solver.output``: (tags or None, interval).  True: every
+    membrane tag; a list of ints: those tags, in that order; absent or False: None (nothing is allocated or launched)."""
+    key = out_cfg.get("save_membrane_potentials", False)
+    interval = int(out_cfg.get("membrane_potential_interval", 1))
+    if interval < 1:
+        raise ValueError("membrane_potential_interval must be at least 1")
+    if key is False or key is None:
+        return None, interval
+    if key is True:
+        return [int(t) for t in gamma_tags], interval
+    if isinstance(key, (list, tuple)) and all(isinstance(t, (int, np.integer)) and not isinstance(t, bool) for t in key):
+        tags = [int(t) for t in key]
+        if len(set(tags)) != len(tags):
+            raise ValueError("save_membrane_potentials lists a tag twice")
+        return tags, interval
+    raise ValueError("save_membrane_potentials must be true or a list of membrane tags")
+
+
 class RunOutput:
     """Everything ``SolverKNPEMI`` records besides the solve itself; one instance per solver."""
 
@@ -181,6 +236,22 @@ class RunOutput:
             os.makedirs(self.prefix, exist_ok=True)
             self.flux_eval = FluxEvaluator(p, [p.membrane_data_tag], mask=True)
             self.fluxes = torch.zeros((solver.time_steps + 1, 2 * p.N_ions), dtype=torch.float64, device=solver.backend.device)
+        # membrane potential per membrane tag and at one probe vertex per tag (output key save_membrane_potentials): one row of
+        # preallocated device tensors per record, read once in save_membrane_potentials()
+        self.phim = None
+        if getattr(solver, "membrane_potential_tags", None) is not None:
+            os.makedirs(self.prefix, exist_ok=True)
+            be = solver.backend
+            tags = solver.membrane_potential_tags
+            be.set_phim_groups([[t] for t in tags])
+            self.phim_lay = be.phim_layout()
+            n_rec = solver.time_steps // solver.membrane_potential_interval + 1
+            self.phim = torch.zeros((n_rec, len(tags), 3), dtype=torch.float64, device=be.device)
+            self.probes = find_membrane_probe_vertices(p, tags)
+            self.probe_cols = np.nonzero(self.probes["owner"] == p.comm.rank)[0]
+            self.probe_idx = torch.as_tensor(self.probes["vertex"][self.probe_cols], dtype=torch.int64, device=be.device)
+            self.probe_fields = [p.phi_m_prev] + ([p.n, p.m, p.h] if hasattr(p, "n") else [])
+            self.probe_rows = torch.zeros((len(self.probe_fields), n_rec, len(self.probe_cols)), dtype=torch.float64, device=be.device)
         self.xdmf = None
         if getattr(solver, "save_xdmfs", False):
             os.makedirs(self.prefix, exist_ok=True)
@@ -217,6 +288,15 @@ class RunOutput:
             self.flux_eval.enqueue(self.fluxes[i])
         if self.budget is not None and (i % s.save_interval == 0):
             s.backend.ion_amounts(self.budget[i // s.save_interval])
+        if self.phim is not None and (i % s.membrane_potential_interval == 0):
+            r = i // s.membrane_potential_interval
+            if s.backend.phim_layout() is not self.phim_lay:           # a membrane_potential(tags=...) call in between replaced the map
+                s.backend.set_phim_groups(self.phim_lay.groups)
+                self.phim_lay = s.backend.phim_layout()
+            s.backend.membrane_potential(out=self.phim[r])
+            if len(self.probe_cols):
+                for k, fn in enumerate(self.probe_fields):
+                    torch.index_select(fn.x.array, 0, self.probe_idx, out=self.probe_rows[k, r])
         if s.save_cpoints and (i % s.save_interval == 0):
             self.checkpoint(i)
         if self.xdmf is not None and i > 0 and (i % s.save_interval == 0):       # reference :471
@@ -398,6 +478,30 @@ class RunOutput:
         data = self._sum_ranks(self.fluxes.cpu().numpy())
         if self.p.comm.rank == 0:
             np.save(self.p.output_dir + "fluxes.npy", data)
+
+    def save_membrane_potentials(self):
+        """phi_m_tags.npy: [records, tags, (mean, min, max)] in V at steps 0, interval, 2 interval, ...; phi_m_tags_index.npy: per tag
+        (tag, area [m^(d-1)]); phi_m_points.npy: [records, tags] phi_m in V at each tag's probe vertex
+        (``find_membrane_probe_vertices``), phi_m_points_xyz.npy: [tags, dim] its coordinates in m; gating_points.npy: [records, tags,
+        (n, m, h)] there when the problem has gating variables.  A tag no facet carries has area 0 and NaN values.  One read-back."""
+        from .diagnostics import reduce_membrane_potential
+        p = self.p
+        lay = self.phim_lay
+        mine = (self.phim.cpu().numpy(), lay.area, self.probe_cols, self.probe_rows.cpu().numpy())
+        parts = p.comm.all_gather_object(mine) if p.comm.size > 1 else [mine]
+        if p.comm.rank != 0:
+            return
+        area, val = reduce_membrane_potential([q[0] for q in parts], [q[1] for q in parts])
+        pts = np.full((len(self.probe_fields), self.phim.shape[0], len(lay.tags)), np.nan)
+        for _, _, cols, rows in parts:
+            pts[:, :, cols] = rows
+        out = p.output_dir
+        np.save(out + "phi_m_tags.npy", val)
+        np.save(out + "phi_m_tags_index.npy", np.stack([lay.tags.astype(np.float64), area], axis=1))
+        np.save(out + "phi_m_points.npy", pts[0])
+        np.save(out + "phi_m_points_xyz.npy", self.probes["xyz"])
+        if len(self.probe_fields) == 4:
+            np.save(out + "gating_points.npy", np.ascontiguousarray(np.transpose(pts[1:], (1, 2, 0))))
 
     def figures(self):
         """PNG plots of the traces (KNPEMIx_solver.py:645-764) when matplotlib is installed; the data are exported either way."""

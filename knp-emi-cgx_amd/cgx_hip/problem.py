@@ -825,6 +825,21 @@ class ProblemKNPEMI(MixedDimensionalProblem):
             flux, area = np.sum([q[0] for q in parts], axis=0), np.sum([q[1] for q in parts], axis=0)
         return {"tag": np.array(tags, dtype=np.int64), "area": area, "flux_i": flux[:, 0, :].copy(), "flux_e": flux[:, 1, :].copy()}
 
+    def membrane_potential(self, tags=None):
+        """Per membrane tag in ``tags`` (default: every tag of ``gamma_tags``, each on its own), over all ranks: ``tag``, ``area``
+        [m^(d-1)] and the area-weighted ``mean``, ``min`` and ``max`` of the nodal phi_m [V] over that tag's facets (mean = the exact
+        P1 integral over the area; min / max over the facets' vertices).  A tag no facet carries has area 0 and NaN values.  One
+        launch pair (knp_diag_membrane_potential) and one read-back."""
+        from .diagnostics import reduce_membrane_potential
+        be = self.create_backend()
+        tags = [int(t) for t in (self.gamma_tags if tags is None else tags)]
+        be.set_phim_groups([[t] for t in tags])
+        part, area = be.membrane_potential().cpu().numpy(), be.phim_layout().area
+        parts = self.comm.all_gather_object((part, area)) if self.comm.size > 1 else [(part, area)]
+        area, val = reduce_membrane_potential([q[0] for q in parts], [q[1] for q in parts])
+        return {"tag": np.array(tags, dtype=np.int64), "area": area, "mean": val[:, 0].copy(), "min": val[:, 1].copy(),
+                "max": val[:, 2].copy()}
+
     def print_conservation(self):
         """Total ion amounts and, per intracellular tag, volume, membrane area and charge: the reference's lines
         (KNPEMIx_problem.py:807-843), printed on rank 0 from ``ion_budget()``."""

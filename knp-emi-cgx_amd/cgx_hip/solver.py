@@ -76,6 +76,10 @@ class SolverKNPEMI:
     save_interval = 20
     save_ion_budget = False   # output key save_ion_budget: ion amounts per cell tag every save_interval steps (ion_budget.npy)
     save_fluxes = False       # output key save_fluxes: ion fluxes across the membrane-data tag at every step (fluxes.npy)
+    # output key save_membrane_potentials (True: every membrane tag, or a list of tags): mean / min / max of phi_m per tag and a probe
+    # vertex per tag every membrane_potential_interval steps (phi_m_tags.npy, phi_m_points.npy); None: off
+    membrane_potential_tags = None
+    membrane_potential_interval = 1
     tot_its = 0.0
     tot_assembly_time = 0.0
     tot_solver_time = 0.0
@@ -112,6 +116,8 @@ class SolverKNPEMI:
         self.save_mat = out.get("save_mat", False)
         self.save_ion_budget = bool(out.get("save_ion_budget", False))
         self.save_fluxes = bool(out.get("save_fluxes", False))
+        from .output import parse_membrane_potential_keys
+        self.membrane_potential_tags, self.membrane_potential_interval = parse_membrane_potential_keys(out, problem.gamma_tags)
         if "save_interval" in out:
             self.save_interval = out["save_interval"]
         self.out_file_prefix = problem.output_dir
@@ -391,7 +397,8 @@ class SolverKNPEMI:
         # traces, probe points, checkpoints (reference :96-99: init_png_savefile / init_checkpoint_file / init_data)
         from .output import RunOutput
         self.output = RunOutput(self) if (self.save_pngs or self.save_dat or self.save_cpoints or self.save_xdmfs or p.point_evaluation
-                                          or self.save_ion_budget or self.save_fluxes) else None
+                                          or self.save_ion_budget or self.save_fluxes
+                                          or self.membrane_potential_tags is not None) else None
         if self.output is not None:
             self.output.record(0)
 
@@ -548,6 +555,8 @@ class SolverKNPEMI:
             self.output.save_ion_budget()
         if self.save_fluxes and self.output is not None:
             self.output.save_fluxes()
+        if self.membrane_potential_tags is not None and self.output is not None:
+            self.output.save_membrane_potentials()
         if self.save_pngs and self.output is not None:
             self.output.figures()
         if self.save_dat:

@@ -1,5 +1,5 @@
 // Diagnostics (knp_diag_*): per-tag volume integrals of the ion fields, per-tag membrane integrals of one bytecode program and
-// per-tag trans-membrane ion fluxes.
+// per-tag trans-membrane ion fluxes, and per-tag integral, minimum and maximum of the membrane potential.
 // Included at the end of knp_kernels.hip, after the host helpers (dev_upload, check_fields, validate_program) it uses.
 //
 // All of them reduce per tag without floating-point atomics.  The items (owned cells / selected membrane facets) are sorted by
@@ -191,6 +191,114 @@ __global__ void __launch_bounds__(NT) k_diag_fluxes(int n, const int32_t* __rest
     diag_chunk_partials<6, NT>(k, live, i == n - 1, v, partial);
 }
 
+// (d) per tag the integral, the minimum and the maximum of the nodal phi_m over the selected membrane facets:
+//   I = sum_F |F|/d sum_a phi(v_a(F)) (exact P1 integral), min / max over all vertices of the tag's facets.
+// The reduction is diag_chunk_partials with the operator triple (+, min, max) on (I, min, max); idle lanes carry its identity.
+struct PhimVal { double s, lo, hi; };
+__device__ __forceinline__ PhimVal phim_identity() { return {0.0, HUGE_VAL, -HUGE_VAL}; }
+// fmin / fmax drop a NaN: a NaN phi_m shows in the integral, not in the minimum and maximum (stated in the ABI comment)
+__device__ __forceinline__ PhimVal phim_op(const PhimVal& a, const PhimVal& b) { return {a.s + b.s, fmin(a.lo, b.lo), fmax(a.hi, b.hi)}; }
+
+template <int BT>
+__device__ __forceinline__ void diag_chunk_partials_phim(int key, bool live, bool last_item, PhimVal v, double* __restrict__ partial) {
+    __shared__ int skey[BT];
+    __shared__ double ss[BT], slo[BT], shi[BT];
+    const int t = threadIdx.x;
+    if (!live) v = phim_identity();
+    skey[t] = live ? key : -1;
+    ss[t] = v.s; slo[t] = v.lo; shi[t] = v.hi;
+    __syncthreads();
+    for (int d = 1; d < BT; d <<= 1) {      // inclusive segmented scan, fixed order: v = left (op) v
+        const bool same = t >= d && skey[t - d] == skey[t];
+        const PhimVal a = same ? PhimVal{ss[t - d], slo[t - d], shi[t - d]} : phim_identity();
+        __syncthreads();
+        v = phim_op(a, v);
+        ss[t] = v.s; slo[t] = v.lo; shi[t] = v.hi;
+        __syncthreads();
+    }
+    if (live && (last_item || t == BT - 1 || skey[t + 1] != key)) {
+        double* o = partial + ((size_t)key + blockIdx.x) * 3;
+        o[0] = v.s; o[1] = v.lo; o[2] = v.hi;
+    }
+}
+
+template <int DIM>
+__global__ void __launch_bounds__(DIAG_BT) k_diag_phim(int n, const int32_t* __restrict__ item, const int32_t* __restrict__ key,
+                                                       const int32_t* __restrict__ fv, const double* __restrict__ fmeas,
+                                                       const double* __restrict__ phim, double* __restrict__ partial) {
+    const int i = blockIdx.x * DIAG_BT + threadIdx.x;
+    const bool live = i < n;
+    PhimVal v = phim_identity();
+    int k = -1;
+    if (live) {
+        k = key[i];
+        const int g = item[i];
+        double s = 0.0;
+#pragma unroll
+        for (int a = 0; a < DIM; ++a) {
+            const double ph = phim[fv[(size_t)g * DIM + a]];
+            s += ph;
+            v.lo = fmin(v.lo, ph);
+            v.hi = fmax(v.hi, ph);
+        }
+        v.s = fmeas[g] * (1.0 / DIM) * s;
+    }
+    diag_chunk_partials_phim<DIAG_BT>(k, live, i == n - 1, v, partial);
+}
+
+__device__ __forceinline__ PhimVal phim_load(const double* __restrict__ partial, int s, int b) {
+    const double* q = partial + ((size_t)s + b) * 3;
+    return {q[0], q[1], q[2]};
+}
+
+// A tag's partials in a fixed order.  Tags of at most PHIM_WAVE_CHUNKS chunks: one wave per tag, one partial per lane, butterfly over
+// the 64 lanes.  The others (k_diag_phim_combine_long, one workgroup per tag of the host-built list): every thread folds the chunks
+// first + tid, first + tid + NT, ... in that order, then a fixed-order tree in LDS.  Which kernel takes a tag depends on its chunk
+// count alone.  Empty tags give (0, +inf, -inf).
+static constexpr int PHIM_WAVE_CHUNKS = 64;
+__global__ void __launch_bounds__(NT) k_diag_phim_combine(int n_tags, int chunk, const int32_t* __restrict__ seg_ptr,
+                                                          const double* __restrict__ partial, double* __restrict__ out) {
+    const int s = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (s >= n_tags) return;              // whole waves
+    const int lo = seg_ptr[s], hi = seg_ptr[s + 1];
+    PhimVal v = phim_identity();
+    if (hi > lo) {
+        const int b0 = lo / chunk, b1 = (hi - 1) / chunk;
+        if (b1 - b0 + 1 > PHIM_WAVE_CHUNKS) return;      // the workgroup kernel's
+        if (b0 + lane <= b1) v = phim_load(partial, s, b0 + lane);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        v.s += __shfl_xor(v.s, o, 64);
+        v.lo = fmin(v.lo, __shfl_xor(v.lo, o, 64));
+        v.hi = fmax(v.hi, __shfl_xor(v.hi, o, 64));
+    }
+    if (lane == 0) { out[(size_t)s * 3] = v.s; out[(size_t)s * 3 + 1] = v.lo; out[(size_t)s * 3 + 2] = v.hi; }
+}
+
+__global__ void __launch_bounds__(NT) k_diag_phim_combine_long(const int32_t* __restrict__ long_tags, int chunk,
+                                                               const int32_t* __restrict__ seg_ptr, const double* __restrict__ partial,
+                                                               double* __restrict__ out) {
+    __shared__ double ss[NT], slo[NT], shi[NT];
+    const int s = long_tags[blockIdx.x];
+    const int t = threadIdx.x;
+    const int b0 = seg_ptr[s] / chunk, b1 = (seg_ptr[s + 1] - 1) / chunk;      // listed tags are not empty
+    PhimVal v = phim_identity();
+    for (int b = b0 + t; b <= b1; b += NT) v = phim_op(v, phim_load(partial, s, b));
+    ss[t] = v.s; slo[t] = v.lo; shi[t] = v.hi;
+    __syncthreads();
+    for (int d = NT / 2; d > 0; d >>= 1) {
+        if (t < d) {
+            ss[t] += ss[t + d];
+            slo[t] = fmin(slo[t], slo[t + d]);
+            shi[t] = fmax(shi[t], shi[t + d]);
+        }
+        __syncthreads();
+    }
+    if (t == 0) { out[(size_t)s * 3] = ss[0]; out[(size_t)s * 3 + 1] = slo[0]; out[(size_t)s * 3 + 2] = shi[0]; }
+}
+
 // a tag's partials in chunk order, one wave per tag; empty tags give zero
 template <int NV>
 __global__ void __launch_bounds__(NT) k_diag_combine(int n_tags, int chunk, const int32_t* __restrict__ seg_ptr,
@@ -224,6 +332,9 @@ void knp_diag_free(knp_ctx* ctx) {
     diag_map_free(ctx->diag_facets);
     diag_map_free(ctx->diag_flux);
     dev_free(ctx->d_flux_rec);
+    diag_map_free(ctx->diag_phim);
+    dev_free(ctx->d_phim_long);
+    ctx->n_phim_long = 0;
     dev_free(ctx->diag_code);
     ctx->diag_n_instr = ctx->diag_n_regs = ctx->diag_n_consts = 0;
     ctx->diag_prog = false;
@@ -502,6 +613,53 @@ int knp_diag_membrane_fluxes(knp_ctx* ctx, const knp_fields* fields, const doubl
         HIPCHK(hipGetLastError());
     }
     return diag_combine(ctx, m, 6, out);
+}
+
+int knp_diag_set_phim_facets(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr, const int32_t* facets) {
+    CHECK_CTX(ctx);
+    KCHK(diag_map_set(ctx, ctx->diag_phim, n_tags, seg_ptr, facets, ctx->g.n_g, DIAG_BT, 3, "phi_m facet map"));
+    dev_free(ctx->d_phim_long);
+    ctx->n_phim_long = 0;
+    std::vector<int32_t> lng;             // the tags the workgroup combine takes: by chunk count alone
+    for (int s = 0; s < n_tags; ++s)
+        if (seg_ptr[s + 1] > seg_ptr[s] && (seg_ptr[s + 1] - 1) / DIAG_BT - seg_ptr[s] / DIAG_BT + 1 > PHIM_WAVE_CHUNKS) lng.push_back(s);
+    if (!lng.empty()) {
+        const int rc = dev_upload(ctx, &ctx->d_phim_long, lng);
+        if (rc != KNP_OK) {               // no half-set map
+            diag_map_free(ctx->diag_phim);
+            dev_free(ctx->d_phim_long);
+            return rc;
+        }
+        ctx->n_phim_long = (int)lng.size();
+    }
+    return KNP_OK;
+}
+
+int knp_diag_membrane_potential(knp_ctx* ctx, const knp_fields* fields, double* out) {
+    CHECK_CTX(ctx);
+    if (!fields || !fields->phi_m) { ctx->err = "null fields or null phi_m field"; return KNP_E_ARG; }
+    if (!out) { ctx->err = "null output buffer"; return KNP_E_ARG; }
+    const KnpDiagMap& m = ctx->diag_phim;
+    if (!m.d_ptr) { ctx->err = "no phi_m facet map (knp_diag_set_phim_facets)"; return KNP_E_STATE; }
+    if (m.n_tags == 0) return KNP_OK;
+    if (m.n > 0) {
+        if (ctx->g.dim == 2)
+            hipLaunchKernelGGL(k_diag_phim<2>, dim3(m.n_chunks), dim3(DIAG_BT), 0, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_fv,
+                               ctx->d_fmeas, fields->phi_m, m.d_partial);
+        else
+            hipLaunchKernelGGL(k_diag_phim<3>, dim3(m.n_chunks), dim3(DIAG_BT), 0, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_fv,
+                               ctx->d_fmeas, fields->phi_m, m.d_partial);
+        HIPCHK(hipGetLastError());
+    }
+    const unsigned nb = (unsigned)((m.n_tags + NT / 64 - 1) / (NT / 64));
+    hipLaunchKernelGGL(k_diag_phim_combine, dim3(nb), dim3(NT), 0, ctx->stream, m.n_tags, m.chunk, m.d_ptr, m.d_partial, out);
+    HIPCHK(hipGetLastError());
+    if (ctx->n_phim_long > 0) {
+        hipLaunchKernelGGL(k_diag_phim_combine_long, dim3(ctx->n_phim_long), dim3(NT), 0, ctx->stream, ctx->d_phim_long, m.chunk, m.d_ptr,
+                           m.d_partial, out);
+        HIPCHK(hipGetLastError());
+    }
+    return KNP_OK;
 }
 
 }  // extern "C"

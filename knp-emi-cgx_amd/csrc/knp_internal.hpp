@@ -377,6 +377,10 @@ struct knp_ctx {
     // trans-membrane ion fluxes (knp_diag_set_flux_facets): a tag map of its own and one time-invariant record per listed facet, in map order
     KnpDiagMap diag_flux;
     double2* d_flux_rec = nullptr;   // [diag_flux.n * (dim == 3 ? 8 : 7)] 16-byte units, layout at k_diag_fluxes
+    // membrane potential per tag (knp_diag_set_phim_facets): a tag map of its own and the tags whose partials a whole workgroup combines
+    KnpDiagMap diag_phim;
+    int32_t* d_phim_long = nullptr;  // [n_phim_long] tags spanning more than 64 chunks
+    int n_phim_long = 0;
     int32_t* diag_code = nullptr;
     int diag_n_instr = 0, diag_n_regs = 0, diag_n_consts = 0;
     double diag_consts[KNP_DIAG_MAX_CONSTS] = {};   // host copy: passed to the kernel by value at every launch
