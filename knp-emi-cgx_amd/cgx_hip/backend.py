@@ -530,30 +530,42 @@ class Backend:
             self._budget = lay
         return self._budget
 
+    def _reduce(self, fn, out, shape, *args):
+        """``fn(ctx, fields, *args, out)``: enqueued, not waited for.  ``out``: a contiguous float64 device tensor of ``shape``'s
+        size, or None for a new one of that shape."""
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=self.device)
+        assert out.is_contiguous() and out.dtype == torch.float64 and out.numel() == int(np.prod(shape))
+        f = self.fields()
+        self.check(fn(self.ctx, C.byref(f), *args, C.c_void_p(out.data_ptr())))
+        return out
+
     def ion_amounts(self, out=None):
         """This rank's amount of each ion per cell tag, [n_tags, 3] on the device: enqueued, not waited for.  ``out``: a
         contiguous float64 device tensor of that shape (a row of a preallocated trace), else a new one."""
-        lay = self.budget_layout()
-        if out is None:
-            out = torch.empty((lay.n_tags, 3), dtype=torch.float64, device=self.device)
-        assert out.is_contiguous() and out.dtype == torch.float64 and out.numel() == 3 * lay.n_tags
-        f = self.fields()
-        self.check(self.lib.knp_diag_volume_integrals(self.ctx, C.byref(f), C.c_void_p(out.data_ptr())))
-        return out
+        return self._reduce(self.lib.knp_diag_volume_integrals, out, (self.budget_layout().n_tags, 3))
 
     def total_ion_amounts(self):
         """int k dx_i + int k dx_e for Na, K, Cl [mol], summed over ranks (print_conservation, KNPEMIx_problem.py:821-827)"""
         loc = self.ion_amounts().sum(dim=0).cpu().numpy()
         return np.array([self.p.comm.allreduce_sum(float(v)) for v in loc])
 
+    def _facet_layout(self, groups, have=None, mask_key=None):
+        """``diagnostics.FacetGroupLayout`` of ``groups`` on this rank: the membrane facets (owner of the first vertex) whose
+        membrane tag is in ``groups[t]`` reduce into slot t, and a facet goes to the first group that lists its tag.  None when
+        ``have``, the (groups, mask key) of the map already set, is the same."""
+        from .diagnostics import FacetGroupLayout
+        groups = tuple(tuple(int(t) for t in g) for g in groups)
+        return None if have == (groups, mask_key) else FacetGroupLayout(self.p, groups)
+
+    def _set_facet_map(self, fn, lay, *more):
+        self.check(fn(self.ctx, lay.n_groups, _i32(lay.seg_ptr), _i32(lay.facets) if lay.facets.size else None, *more))
+
     def set_facet_groups(self, groups):
-        """Membrane facets of this rank (owner of the first vertex) whose membrane tag is in ``groups[t]``, reduced into slot t
-        of ``membrane_integral``; a facet goes to the first group that lists its tag"""
-        from .diagnostics import facet_group_map
-        seg_ptr, facets = facet_group_map(self.p, groups)
-        self.check(self.lib.knp_diag_set_facet_tags(self.ctx, len(groups), _i32(seg_ptr), _i32(facets) if facets.size else None))
-        self._keep += [seg_ptr, facets]
-        self.n_facet_groups = len(groups)
+        """The facet groups of ``membrane_integral`` (``_facet_layout``)"""
+        lay = self._facet_layout(groups)
+        self._set_facet_map(self.lib.knp_diag_set_facet_tags, lay)
+        self.n_facet_groups = lay.n_groups
 
     def set_diag_program(self, spec):
         code = np.ascontiguousarray(spec.code, dtype=np.int32)
@@ -568,29 +580,21 @@ class Backend:
 
     def membrane_integral(self, out):
         """integral of the diagnostic program over each facet group into the device tensor ``out`` [n_groups] (enqueued)"""
-        assert out.is_contiguous() and out.dtype == torch.float64 and out.numel() == self.n_facet_groups
-        f = self.fields()
-        self.check(self.lib.knp_diag_membrane_integral(self.ctx, C.byref(f), C.c_void_p(out.data_ptr())))
-        return out
+        return self._reduce(self.lib.knp_diag_membrane_integral, out, (self.n_facet_groups,))
 
     def set_flux_groups(self, groups, mask=None):
-        """Membrane facets of this rank (owner of the first vertex) whose membrane tag is in ``groups[t]``, reduced into slot t of
-        ``membrane_fluxes``; ``mask``: None or an open box ``(lo, hi)`` in metres (``diagnostics.stimulus_box``).  Builds the
-        per-facet records (knp_diag_set_flux_facets); a call with the groups and mask already set does nothing.  The map is
-        apart from the one of ``set_facet_groups``."""
-        from .diagnostics import facet_areas, facet_group_map
-        groups = tuple(tuple(int(t) for t in g) for g in groups)
+        """The facet groups of ``membrane_fluxes`` (``_facet_layout``); ``mask``: None or an open box ``(lo, hi)`` in metres
+        (``diagnostics.stimulus_box``).  Builds the per-facet records (knp_diag_set_flux_facets); a call with the groups and mask
+        already set does nothing.  The map is apart from the one of ``set_facet_groups``."""
         box = None if mask is None else (np.ascontiguousarray(mask[0], dtype=np.float64), np.ascontiguousarray(mask[1], dtype=np.float64))
-        key = (groups, None if box is None else (box[0].tobytes(), box[1].tobytes()))
-        if getattr(self, "_flux_key", None) == key:
+        mask_key = None if box is None else (box[0].tobytes(), box[1].tobytes())
+        lay = self._facet_layout(groups, getattr(self, "_flux_key", None), mask_key)
+        if lay is None:
             return
-        seg_ptr, facets = facet_group_map(self.p, groups)
         self._flux_key = None
-        self.check(self.lib.knp_diag_set_flux_facets(self.ctx, len(groups), _i32(seg_ptr), _i32(facets) if facets.size else None,
-                                                     _f64(box[0]) if box else None, _f64(box[1]) if box else None))
-        self._flux_key = key
-        self.n_flux_groups = len(groups)
-        self.flux_area = facet_areas(self.p, seg_ptr, facets)
+        self._set_facet_map(self.lib.knp_diag_set_flux_facets, lay, _f64(box[0]) if box else None, _f64(box[1]) if box else None)
+        self._flux_key = (lay.groups, mask_key)
+        self.n_flux_groups, self.flux_area = lay.n_groups, lay.area
 
     def membrane_fluxes(self, out=None):
         """This rank's molar flux of every ion out of each side through each facet group, [n_groups, 2 (intra, extra), 3] on the
@@ -599,26 +603,19 @@ class Backend:
         p = self.p
         if getattr(self, "_flux_key", None) is None:
             raise KnpError("membrane_fluxes() before set_flux_groups()")
-        if out is None:
-            out = torch.empty((self.n_flux_groups, 2, 3), dtype=torch.float64, device=self.device)
-        assert out.is_contiguous() and out.dtype == torch.float64 and out.numel() == 6 * self.n_flux_groups
         D, zp = flux_coefficients(p)
-        f = self.fields()
-        self.check(self.lib.knp_diag_membrane_fluxes(self.ctx, C.byref(f), C.c_void_p(p.wh[0][p.N_ions].data_ptr()),
-                                                     C.c_void_p(p.wh[1][p.N_ions].data_ptr()), _f64(D), _f64(zp), C.c_void_p(out.data_ptr())))
-        return out
+        return self._reduce(self.lib.knp_diag_membrane_fluxes, out, (self.n_flux_groups, 2, 3), C.c_void_p(p.wh[0][p.N_ions].data_ptr()),
+                            C.c_void_p(p.wh[1][p.N_ions].data_ptr()), _f64(D), _f64(zp))
 
     def set_phim_groups(self, groups):
-        """Membrane facets of this rank (owner of the first vertex) whose membrane tag is in ``groups[t]``, reduced into slot t of
-        ``membrane_potential`` (knp_diag_set_phim_facets); a call with the groups already set does nothing.  The map is apart from
-        the ones of ``set_facet_groups`` and ``set_flux_groups``."""
-        from .diagnostics import PhimLayout
-        groups = tuple(tuple(int(t) for t in g) for g in groups)
-        if getattr(self, "_phim", None) is not None and self._phim.groups == groups:
+        """The facet groups of ``membrane_potential`` (``_facet_layout``, knp_diag_set_phim_facets); a call with the groups already
+        set does nothing.  The map is apart from the ones of ``set_facet_groups`` and ``set_flux_groups``."""
+        have = getattr(self, "_phim", None)
+        lay = self._facet_layout(groups, have and (have.groups, None))
+        if lay is None:
             return
-        lay = PhimLayout(self.p, groups)
         self._phim = None
-        self.check(self.lib.knp_diag_set_phim_facets(self.ctx, len(groups), _i32(lay.seg_ptr), _i32(lay.facets) if lay.facets.size else None))
+        self._set_facet_map(self.lib.knp_diag_set_phim_facets, lay)
         self._phim = lay
 
     def phim_layout(self):
@@ -631,13 +628,7 @@ class Backend:
         """This rank's (integral of phi_m [V m^(d-1)], minimum, maximum [V]) over each facet group, [n_groups, 3] on the device:
         enqueued, not waited for; a group without facets here gives (0, +inf, -inf).  ``out``: a contiguous float64 device tensor
         of that size (a row of a preallocated trace), else a new one."""
-        lay = self.phim_layout()
-        if out is None:
-            out = torch.empty((lay.n_groups, 3), dtype=torch.float64, device=self.device)
-        assert out.is_contiguous() and out.dtype == torch.float64 and out.numel() == 3 * lay.n_groups
-        f = self.fields()
-        self.check(self.lib.knp_diag_membrane_potential(self.ctx, C.byref(f), C.c_void_p(out.data_ptr())))
-        return out
+        return self._reduce(self.lib.knp_diag_membrane_potential, out, (self.phim_layout().n_groups, 3))
 
     # ---- exports (parity hooks) ------------------------------------------------------------
     def csr(self):

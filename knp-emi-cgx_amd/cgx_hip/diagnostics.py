@@ -106,9 +106,10 @@ def facet_areas(problem, seg_ptr, facets):
     return np.bincount(dense, weights=problem._fmeas[facets], minlength=len(seg_ptr) - 1).astype(np.float64)
 
 
-class PhimLayout:
-    """The facet groups of the membrane-potential reduction on this rank: ``groups`` (tuples of membrane tags), ``tags`` (each
-    group's first tag), the facet map (``facet_group_map``) and ``area``, this rank's part of A_t = sum_F |F| per group."""
+class FacetGroupLayout:
+    """Facet groups of a membrane reduction (fluxes, membrane potential, membrane integral) on this rank: ``groups`` (tuples of
+    membrane tags), ``tags`` (each group's first tag), the facet map (``facet_group_map``) and ``area``, this rank's part of
+    A_t = sum_F |F| per group."""
 
     def __init__(self, problem, groups):
         self.groups = tuple(tuple(int(t) for t in g) for g in groups)

@@ -5,32 +5,62 @@
 // All of them reduce per tag without floating-point atomics.  The items (owned cells / selected membrane facets) are sorted by
 // their dense tag index on the host, once; a block takes a fixed-size chunk of consecutive items, sums each run of equal tags inside
 // the chunk with a segmented scan in LDS and stores one partial per (chunk, tag) pair at index tag + chunk (unique: consecutive
-// chunks share at most their boundary tag).  A second pass adds a tag's partials in chunk order, one wave per tag.  The work split
-// depends on the item count only, never on how the items fall into tags, and the result is the same bits on every run.
+// chunks share at most their boundary tag).  A second pass folds a tag's partials in a fixed order (k_diag_combine, and for the long
+// tags of a map that asks for it k_diag_combine_long).  The work split depends on the item count only, never on how the items fall
+// into tags, and the result is the same bits on every run.
+
+// What a reduction reduces: N doubles per item, the operator op(left, right) and its identity.  The scan and the combines below
+// are written once, for any such type.
+template <int NV>
+struct DiagSum {          // NV sums
+    static constexpr int N = NV;
+    double v[NV];
+    __device__ static DiagSum identity() {
+        DiagSum r;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) r.v[j] = 0.0;
+        return r;
+    }
+    __device__ static DiagSum op(const DiagSum& a, const DiagSum& b) {
+        DiagSum r;
+#pragma unroll
+        for (int j = 0; j < NV; ++j) r.v[j] = a.v[j] + b.v[j];
+        return r;
+    }
+};
+struct DiagPhim {         // (integral, minimum, maximum) of phi_m
+    static constexpr int N = 3;
+    double v[3];
+    __device__ static DiagPhim identity() { return {{0.0, HUGE_VAL, -HUGE_VAL}}; }
+    // fmin / fmax drop a NaN: a NaN phi_m shows in the integral, not in the minimum and maximum (stated in the ABI comment)
+    __device__ static DiagPhim op(const DiagPhim& a, const DiagPhim& b) { return {{a.v[0] + b.v[0], fmin(a.v[1], b.v[1]), fmax(a.v[2], b.v[2])}}; }
+};
 
 // One partial per run of equal keys inside the block's chunk (keys ascending over the live threads, which form a prefix).
-template <int NV, int BT>
-__device__ __forceinline__ void diag_chunk_partials(int key, bool live, bool last_item, const double (&v)[NV], double* __restrict__ partial) {
+template <class V, int BT>
+__device__ __forceinline__ void diag_chunk_partials(int key, bool live, bool last_item, V v, double* __restrict__ partial) {
     __shared__ int skey[BT];
-    __shared__ double sv[NV][BT];
+    __shared__ double sv[V::N][BT];
     const int t = threadIdx.x;
+    if (!live) v = V::identity();
     skey[t] = live ? key : -1;
 #pragma unroll
-    for (int j = 0; j < NV; ++j) sv[j][t] = live ? v[j] : 0.0;
+    for (int j = 0; j < V::N; ++j) sv[j][t] = v.v[j];
     __syncthreads();
-    for (int d = 1; d < BT; d <<= 1) {      // inclusive segmented scan, fixed order
-        double a[NV];
+    for (int d = 1; d < BT; d <<= 1) {      // inclusive segmented scan, fixed order: v = left (op) v
         const bool same = t >= d && skey[t - d] == skey[t];
+        V left = V::identity();
 #pragma unroll
-        for (int j = 0; j < NV; ++j) a[j] = same ? sv[j][t - d] : 0.0;
+        for (int j = 0; j < V::N; ++j) left.v[j] = same ? sv[j][t - d] : left.v[j];
         __syncthreads();
+        v = V::op(left, v);
 #pragma unroll
-        for (int j = 0; j < NV; ++j) sv[j][t] += a[j];
+        for (int j = 0; j < V::N; ++j) sv[j][t] = v.v[j];
         __syncthreads();
     }
     if (live && (last_item || t == BT - 1 || skey[t + 1] != key)) {
 #pragma unroll
-        for (int j = 0; j < NV; ++j) partial[((size_t)key + blockIdx.x) * NV + j] = sv[j][t];
+        for (int j = 0; j < V::N; ++j) partial[((size_t)key + blockIdx.x) * V::N + j] = v.v[j];
     }
 }
 
@@ -41,7 +71,7 @@ __global__ void __launch_bounds__(NT) k_diag_cells(int n, const int32_t* __restr
                                                    const double* __restrict__ coords, FieldPtrs f, double* __restrict__ partial) {
     const int i = blockIdx.x * NT + threadIdx.x;
     const bool live = i < n;
-    double v[3] = {0.0, 0.0, 0.0};
+    DiagSum<3> v = DiagSum<3>::identity();
     int k = -1;
     if (live) {
         const int c = item[i];
@@ -65,10 +95,10 @@ __global__ void __launch_bounds__(NT) k_diag_cells(int n, const int32_t* __restr
             double s = 0.0;
 #pragma unroll
             for (int a = 0; a <= DIM; ++a) s += fj[vv[a]];
-            v[j] = w * s;
+            v.v[j] = w * s;
         }
     }
-    diag_chunk_partials<3, NT>(k, live, i == n - 1, v, partial);
+    diag_chunk_partials<DiagSum<3>, NT>(k, live, i == n - 1, v, partial);
 }
 
 // (b) integral over the selected membrane facets of the sum of a program's outputs: quadrature points q, weights q_w |F|
@@ -131,8 +161,7 @@ __global__ void __launch_bounds__(DIAG_BT) k_diag_facets(int n, const int32_t* _
         run_program<1, DIAG_BT>(code, n_instr, sk, kiq, keq, phq, auxq, xq, Iout, reg);
         acc += qw[q] * meas * (Iout[0][0] + Iout[0][1] + Iout[0][2]);
     }
-    const double val[1] = {acc};
-    diag_chunk_partials<1, DIAG_BT>(live ? key[i] : -1, live, i == n - 1, val, partial);
+    diag_chunk_partials<DiagSum<1>, DIAG_BT>(live ? key[i] : -1, live, i == n - 1, DiagSum<1>{{acc}}, partial);
 }
 
 // (c) molar flux of every ion through the selected membrane facets, on both sides:
@@ -152,7 +181,7 @@ __global__ void __launch_bounds__(NT) k_diag_fluxes(int n, const int32_t* __rest
     constexpr int UNITS = FluxRecord<DIM>::UNITS, ND = 2 * (UNITS - 2);
     const int i = blockIdx.x * NT + threadIdx.x;
     const bool live = i < n;
-    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    DiagSum<6> v = DiagSum<6>::identity();
     int k = -1;
     if (live) {
         k = key[i];
@@ -184,51 +213,23 @@ __global__ void __launch_bounds__(NT) k_diag_fluxes(int n, const int32_t* __rest
                     gc += g[a] * ca;
                     if (a < DIM) wc += d[2 * (DIM + 1) + 1 + a] * ca;
                 }
-                v[3 * s + j] = -K.D[j] * (W0 * gc + K.zp[j] * wc * gphi);
+                v.v[3 * s + j] = -K.D[j] * (W0 * gc + K.zp[j] * wc * gphi);
             }
         }
     }
-    diag_chunk_partials<6, NT>(k, live, i == n - 1, v, partial);
+    diag_chunk_partials<DiagSum<6>, NT>(k, live, i == n - 1, v, partial);
 }
 
 // (d) per tag the integral, the minimum and the maximum of the nodal phi_m over the selected membrane facets:
 //   I = sum_F |F|/d sum_a phi(v_a(F)) (exact P1 integral), min / max over all vertices of the tag's facets.
-// The reduction is diag_chunk_partials with the operator triple (+, min, max) on (I, min, max); idle lanes carry its identity.
-struct PhimVal { double s, lo, hi; };
-__device__ __forceinline__ PhimVal phim_identity() { return {0.0, HUGE_VAL, -HUGE_VAL}; }
-// fmin / fmax drop a NaN: a NaN phi_m shows in the integral, not in the minimum and maximum (stated in the ABI comment)
-__device__ __forceinline__ PhimVal phim_op(const PhimVal& a, const PhimVal& b) { return {a.s + b.s, fmin(a.lo, b.lo), fmax(a.hi, b.hi)}; }
-
-template <int BT>
-__device__ __forceinline__ void diag_chunk_partials_phim(int key, bool live, bool last_item, PhimVal v, double* __restrict__ partial) {
-    __shared__ int skey[BT];
-    __shared__ double ss[BT], slo[BT], shi[BT];
-    const int t = threadIdx.x;
-    if (!live) v = phim_identity();
-    skey[t] = live ? key : -1;
-    ss[t] = v.s; slo[t] = v.lo; shi[t] = v.hi;
-    __syncthreads();
-    for (int d = 1; d < BT; d <<= 1) {      // inclusive segmented scan, fixed order: v = left (op) v
-        const bool same = t >= d && skey[t - d] == skey[t];
-        const PhimVal a = same ? PhimVal{ss[t - d], slo[t - d], shi[t - d]} : phim_identity();
-        __syncthreads();
-        v = phim_op(a, v);
-        ss[t] = v.s; slo[t] = v.lo; shi[t] = v.hi;
-        __syncthreads();
-    }
-    if (live && (last_item || t == BT - 1 || skey[t + 1] != key)) {
-        double* o = partial + ((size_t)key + blockIdx.x) * 3;
-        o[0] = v.s; o[1] = v.lo; o[2] = v.hi;
-    }
-}
-
+// The reduction is DiagPhim's: the operator triple (+, min, max) on (I, min, max); idle lanes carry its identity.
 template <int DIM>
 __global__ void __launch_bounds__(DIAG_BT) k_diag_phim(int n, const int32_t* __restrict__ item, const int32_t* __restrict__ key,
                                                        const int32_t* __restrict__ fv, const double* __restrict__ fmeas,
                                                        const double* __restrict__ phim, double* __restrict__ partial) {
     const int i = blockIdx.x * DIAG_BT + threadIdx.x;
     const bool live = i < n;
-    PhimVal v = phim_identity();
+    DiagPhim v = DiagPhim::identity();
     int k = -1;
     if (live) {
         k = key[i];
@@ -238,93 +239,83 @@ __global__ void __launch_bounds__(DIAG_BT) k_diag_phim(int n, const int32_t* __r
         for (int a = 0; a < DIM; ++a) {
             const double ph = phim[fv[(size_t)g * DIM + a]];
             s += ph;
-            v.lo = fmin(v.lo, ph);
-            v.hi = fmax(v.hi, ph);
+            v.v[1] = fmin(v.v[1], ph);
+            v.v[2] = fmax(v.v[2], ph);
         }
-        v.s = fmeas[g] * (1.0 / DIM) * s;
+        v.v[0] = fmeas[g] * (1.0 / DIM) * s;
     }
-    diag_chunk_partials_phim<DIAG_BT>(k, live, i == n - 1, v, partial);
+    diag_chunk_partials<DiagPhim, DIAG_BT>(k, live, i == n - 1, v, partial);
 }
 
-__device__ __forceinline__ PhimVal phim_load(const double* __restrict__ partial, int s, int b) {
-    const double* q = partial + ((size_t)s + b) * 3;
-    return {q[0], q[1], q[2]};
-}
-
-// A tag's partials in a fixed order.  Tags of at most PHIM_WAVE_CHUNKS chunks: one wave per tag, one partial per lane, butterfly over
-// the 64 lanes.  The others (k_diag_phim_combine_long, one workgroup per tag of the host-built list): every thread folds the chunks
-// first + tid, first + tid + NT, ... in that order, then a fixed-order tree in LDS.  Which kernel takes a tag depends on its chunk
-// count alone.  Empty tags give (0, +inf, -inf).
-static constexpr int PHIM_WAVE_CHUNKS = 64;
-__global__ void __launch_bounds__(NT) k_diag_phim_combine(int n_tags, int chunk, const int32_t* __restrict__ seg_ptr,
-                                                          const double* __restrict__ partial, double* __restrict__ out) {
-    const int s = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
-    const int lane = threadIdx.x & 63;
-    if (s >= n_tags) return;              // whole waves
-    const int lo = seg_ptr[s], hi = seg_ptr[s + 1];
-    PhimVal v = phim_identity();
-    if (hi > lo) {
-        const int b0 = lo / chunk, b1 = (hi - 1) / chunk;
-        if (b1 - b0 + 1 > PHIM_WAVE_CHUNKS) return;      // the workgroup kernel's
-        if (b0 + lane <= b1) v = phim_load(partial, s, b0 + lane);
-    }
+template <class V>
+__device__ __forceinline__ V diag_load(const double* __restrict__ partial, int s, int b) {
+    V r;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        v.s += __shfl_xor(v.s, o, 64);
-        v.lo = fmin(v.lo, __shfl_xor(v.lo, o, 64));
-        v.hi = fmax(v.hi, __shfl_xor(v.hi, o, 64));
-    }
-    if (lane == 0) { out[(size_t)s * 3] = v.s; out[(size_t)s * 3 + 1] = v.lo; out[(size_t)s * 3 + 2] = v.hi; }
+    for (int j = 0; j < V::N; ++j) r.v[j] = partial[((size_t)s + b) * V::N + j];
+    return r;
+}
+template <class V>
+__device__ __forceinline__ void diag_store(double* __restrict__ out, int s, const V& v) {
+#pragma unroll
+    for (int j = 0; j < V::N; ++j) out[(size_t)s * V::N + j] = v.v[j];
 }
 
-__global__ void __launch_bounds__(NT) k_diag_phim_combine_long(const int32_t* __restrict__ long_tags, int chunk,
-                                                               const int32_t* __restrict__ seg_ptr, const double* __restrict__ partial,
-                                                               double* __restrict__ out) {
-    __shared__ double ss[NT], slo[NT], shi[NT];
-    const int s = long_tags[blockIdx.x];
-    const int t = threadIdx.x;
-    const int b0 = seg_ptr[s] / chunk, b1 = (seg_ptr[s + 1] - 1) / chunk;      // listed tags are not empty
-    PhimVal v = phim_identity();
-    for (int b = b0 + t; b <= b1; b += NT) v = phim_op(v, phim_load(partial, s, b));
-    ss[t] = v.s; slo[t] = v.lo; shi[t] = v.hi;
-    __syncthreads();
-    for (int d = NT / 2; d > 0; d >>= 1) {
-        if (t < d) {
-            ss[t] += ss[t + d];
-            slo[t] = fmin(slo[t], slo[t + d]);
-            shi[t] = fmax(shi[t], shi[t + d]);
-        }
-        __syncthreads();
-    }
-    if (t == 0) { out[(size_t)s * 3] = ss[0]; out[(size_t)s * 3 + 1] = slo[0]; out[(size_t)s * 3 + 2] = shi[0]; }
-}
-
-// a tag's partials in chunk order, one wave per tag; empty tags give zero
-template <int NV>
-__global__ void __launch_bounds__(NT) k_diag_combine(int n_tags, int chunk, const int32_t* __restrict__ seg_ptr,
+// A tag's partials in a fixed order; empty tags give the identity.  k_diag_combine, one wave per tag: lane l folds the chunks
+// first + l, first + l + 64, ... in that order, then a butterfly over the 64 lanes.  A map with wave_chunks > 0 gives its tags of
+// more chunks than that to k_diag_combine_long instead, one workgroup per tag of the map's host-built list: thread t folds the
+// chunks first + t, first + t + NT, ..., then a fixed-order tree in LDS.  Which kernel takes a tag depends on its chunk count alone.
+template <class V>
+__global__ void __launch_bounds__(NT) k_diag_combine(int n_tags, int chunk, int wave_chunks, const int32_t* __restrict__ seg_ptr,
                                                      const double* __restrict__ partial, double* __restrict__ out) {
     const int s = blockIdx.x * (NT / 64) + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (s >= n_tags) return;              // whole waves
     const int lo = seg_ptr[s], hi = seg_ptr[s + 1];
-    double acc[NV];
-#pragma unroll
-    for (int j = 0; j < NV; ++j) acc[j] = 0.0;
+    V v = V::identity();
     if (hi > lo) {
-        const int b1 = (hi - 1) / chunk;
-        for (int b = lo / chunk + lane; b <= b1; b += 64)
-#pragma unroll
-            for (int j = 0; j < NV; ++j) acc[j] += partial[((size_t)s + b) * NV + j];
+        const int b0 = lo / chunk, b1 = (hi - 1) / chunk;
+        if (wave_chunks > 0 && b1 - b0 + 1 > wave_chunks) return;      // the workgroup kernel's
+        for (int b = b0 + lane; b <= b1; b += 64) v = V::op(v, diag_load<V>(partial, s, b));
     }
 #pragma unroll
-    for (int j = 0; j < NV; ++j) acc[j] = wave_sum(acc[j]);
-    if (lane == 0)
+    for (int o = 32; o > 0; o >>= 1) {
+        V w;
 #pragma unroll
-        for (int j = 0; j < NV; ++j) out[(size_t)s * NV + j] = acc[j];
+        for (int j = 0; j < V::N; ++j) w.v[j] = __shfl_xor(v.v[j], o, 64);
+        v = V::op(v, w);
+    }
+    if (lane == 0) diag_store(out, s, v);
+}
+
+template <class V>
+__global__ void __launch_bounds__(NT) k_diag_combine_long(const int32_t* __restrict__ long_tags, int chunk,
+                                                          const int32_t* __restrict__ seg_ptr, const double* __restrict__ partial,
+                                                          double* __restrict__ out) {
+    __shared__ double sv[V::N][NT];
+    const int s = long_tags[blockIdx.x];
+    const int t = threadIdx.x;
+    const int b0 = seg_ptr[s] / chunk, b1 = (seg_ptr[s + 1] - 1) / chunk;      // listed tags are not empty
+    V v = V::identity();
+    for (int b = b0 + t; b <= b1; b += NT) v = V::op(v, diag_load<V>(partial, s, b));
+#pragma unroll
+    for (int j = 0; j < V::N; ++j) sv[j][t] = v.v[j];
+    __syncthreads();
+    for (int d = NT / 2; d > 0; d >>= 1) {
+        if (t < d) {
+            V w;
+#pragma unroll
+            for (int j = 0; j < V::N; ++j) w.v[j] = sv[j][t + d];
+            v = V::op(v, w);
+#pragma unroll
+            for (int j = 0; j < V::N; ++j) sv[j][t] = v.v[j];
+        }
+        __syncthreads();
+    }
+    if (t == 0) diag_store(out, s, v);
 }
 
 static void diag_map_free(KnpDiagMap& m) {
-    dev_free(m.d_ptr); dev_free(m.d_item); dev_free(m.d_key); dev_free(m.d_partial);
+    dev_free(m.d_ptr); dev_free(m.d_item); dev_free(m.d_key); dev_free(m.d_partial); dev_free(m.d_long);
     m = KnpDiagMap();
 }
 void knp_diag_free(knp_ctx* ctx) {
@@ -333,21 +324,20 @@ void knp_diag_free(knp_ctx* ctx) {
     diag_map_free(ctx->diag_flux);
     dev_free(ctx->d_flux_rec);
     diag_map_free(ctx->diag_phim);
-    dev_free(ctx->d_phim_long);
-    ctx->n_phim_long = 0;
     dev_free(ctx->diag_code);
     ctx->diag_n_instr = ctx->diag_n_regs = ctx->diag_n_consts = 0;
     ctx->diag_prog = false;
 }
 
-// validate a host tag map (items in [0, n_items), each at most once, seg_ptr non-decreasing from 0) and upload it with its scratch
+// validate a host tag map (items in [0, n_items), each at most once, seg_ptr non-decreasing from 0) and upload it with its scratch;
+// wave_chunks > 0: the tags of more chunks than that go on the list of k_diag_combine_long.  A failed upload leaves no map.
 static int diag_map_set(knp_ctx* ctx, KnpDiagMap& m, int n_tags, const int32_t* seg_ptr, const int32_t* items, int n_items, int chunk,
-                        int nv, const char* what) {
+                        int nv, int wave_chunks, const char* what) {
     if (n_tags < 0 || (n_tags > 0 && !seg_ptr)) { ctx->err = std::string(what) + ": bad tag count or null seg_ptr"; return KNP_E_ARG; }
     const int n = n_tags > 0 ? seg_ptr[n_tags] : 0;
     if (n_tags > 0 && seg_ptr[0] != 0) { ctx->err = std::string(what) + ": seg_ptr[0] must be 0"; return KNP_E_ARG; }
     if (n < 0 || n > n_items || (n > 0 && !items)) { ctx->err = std::string(what) + ": more items than the mesh has, or null items"; return KNP_E_ARG; }
-    std::vector<int32_t> key((size_t)n);
+    std::vector<int32_t> key((size_t)n), lng;
     std::vector<uint8_t> seen((size_t)std::max(n_items, 1), 0);
     for (int s = 0; s < n_tags; ++s) {
         if (seg_ptr[s + 1] < seg_ptr[s]) { ctx->err = std::string(what) + ": seg_ptr must be non-decreasing"; return KNP_E_ARG; }
@@ -357,35 +347,54 @@ static int diag_map_set(knp_ctx* ctx, KnpDiagMap& m, int n_tags, const int32_t* 
             seen[it] = 1;
             key[i] = s;
         }
+        if (wave_chunks > 0 && seg_ptr[s + 1] > seg_ptr[s] && (seg_ptr[s + 1] - 1) / chunk - seg_ptr[s] / chunk + 1 > wave_chunks) lng.push_back(s);
     }
     HIPCHK(hipStreamSynchronize(ctx->stream));   // a diagnostic in flight may still read the old map
     diag_map_free(m);
     std::vector<int32_t> ptr(seg_ptr, seg_ptr + (n_tags > 0 ? n_tags + 1 : 0));
     std::vector<int32_t> itv(items, items + n);
-    KCHK(dev_upload(ctx, &m.d_ptr, ptr));
-    KCHK(dev_upload(ctx, &m.d_item, itv));
-    KCHK(dev_upload(ctx, &m.d_key, key));
     m.n_tags = n_tags;
     m.n = n;
     m.chunk = chunk;
     m.n_chunks = (n + chunk - 1) / chunk;
+    m.wave_chunks = wave_chunks;
+    m.n_long = (int)lng.size();
     const size_t np = (size_t)(n_tags + m.n_chunks) * nv;
-    HIPCHK(hipMalloc((void**)&m.d_partial, std::max<size_t>(np, 1) * sizeof(double)));
+    const int rc = [&]() -> int {
+        KCHK(dev_upload(ctx, &m.d_ptr, ptr));
+        KCHK(dev_upload(ctx, &m.d_item, itv));
+        KCHK(dev_upload(ctx, &m.d_key, key));
+        if (m.n_long > 0) KCHK(dev_upload(ctx, &m.d_long, lng));
+        HIPCHK(hipMalloc((void**)&m.d_partial, std::max<size_t>(np, 1) * sizeof(double)));
+        return KNP_OK;
+    }();
+    if (rc != KNP_OK) diag_map_free(m);
+    return rc;
+}
+
+template <class V>
+static int diag_combine(knp_ctx* ctx, const KnpDiagMap& m, double* out) {
+    if (m.n_tags == 0) return KNP_OK;
+    const unsigned nb = (unsigned)((m.n_tags + NT / 64 - 1) / (NT / 64));
+    hipLaunchKernelGGL(k_diag_combine<V>, dim3(nb), dim3(NT), 0, ctx->stream, m.n_tags, m.chunk, m.wave_chunks, m.d_ptr, m.d_partial, out);
+    HIPCHK(hipGetLastError());
+    if (m.n_long > 0) {
+        hipLaunchKernelGGL(k_diag_combine_long<V>, dim3(m.n_long), dim3(NT), 0, ctx->stream, m.d_long, m.chunk, m.d_ptr, m.d_partial, out);
+        HIPCHK(hipGetLastError());
+    }
     return KNP_OK;
 }
 
-static int diag_combine(knp_ctx* ctx, const KnpDiagMap& m, int nv, double* out) {
-    if (m.n_tags == 0) return KNP_OK;
-    const unsigned nb = (unsigned)((m.n_tags + NT / 64 - 1) / (NT / 64));
-    if (nv == 6)
-        hipLaunchKernelGGL(k_diag_combine<6>, dim3(nb), dim3(NT), 0, ctx->stream, m.n_tags, m.chunk, m.d_ptr, m.d_partial, out);
-    else if (nv == 3)
-        hipLaunchKernelGGL(k_diag_combine<3>, dim3(nb), dim3(NT), 0, ctx->stream, m.n_tags, m.chunk, m.d_ptr, m.d_partial, out);
-    else
-        hipLaunchKernelGGL(k_diag_combine<1>, dim3(nb), dim3(NT), 0, ctx->stream, m.n_tags, m.chunk, m.d_ptr, m.d_partial, out);
-    HIPCHK(hipGetLastError());
+// the last two argument checks of every reduction: an output buffer and a map
+static int diag_check(knp_ctx* ctx, const double* out, bool have_map, const char* no_map) {
+    if (!out) { ctx->err = "null output buffer"; return KNP_E_ARG; }
+    if (!have_map) { ctx->err = no_map; return KNP_E_STATE; }
     return KNP_OK;
 }
+
+// f(std::integral_constant<int, DIM>()) for the mesh's dimension
+template <class F>
+static auto by_dim(int dim, F&& f) { return dim == 2 ? f(std::integral_constant<int, 2>()) : f(std::integral_constant<int, 3>()); }
 
 // gradients of the barycentric coordinates of the simplex x[0..DIM] (rows of DIM coordinates): G[a] = grad(lambda_a); false when flat
 template <int DIM>
@@ -477,31 +486,28 @@ extern "C" {
 
 int knp_diag_set_cell_tags(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr, const int32_t* cells) {
     CHECK_CTX(ctx);
-    return diag_map_set(ctx, ctx->diag_cells, n_tags, seg_ptr, cells, ctx->g.n_c_owned, NT, 3, "cell tag map");
+    return diag_map_set(ctx, ctx->diag_cells, n_tags, seg_ptr, cells, ctx->g.n_c_owned, NT, 3, 0, "cell tag map");
 }
 
 int knp_diag_volume_integrals(knp_ctx* ctx, const knp_fields* fields, double* out) {
     CHECK_CTX(ctx);
     KCHK(check_fields(ctx, fields, false));
-    if (!out) { ctx->err = "null output buffer"; return KNP_E_ARG; }
     const KnpDiagMap& m = ctx->diag_cells;
-    if (!m.d_ptr) { ctx->err = "no cell tag map (knp_diag_set_cell_tags)"; return KNP_E_STATE; }
+    KCHK(diag_check(ctx, out, m.d_ptr, "no cell tag map (knp_diag_set_cell_tags)"));
     const FieldPtrs f = make_fields(fields);
     if (m.n > 0) {
-        if (ctx->g.dim == 2)
-            hipLaunchKernelGGL(k_diag_cells<2>, dim3(m.n_chunks), dim3(NT), 0, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_cells,
+        by_dim(ctx->g.dim, [&](auto D) {
+            hipLaunchKernelGGL(k_diag_cells<D()>, dim3(m.n_chunks), dim3(NT), 0, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_cells,
                                ctx->d_cell_side, ctx->d_coords, f, m.d_partial);
-        else
-            hipLaunchKernelGGL(k_diag_cells<3>, dim3(m.n_chunks), dim3(NT), 0, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_cells,
-                               ctx->d_cell_side, ctx->d_coords, f, m.d_partial);
+        });
         HIPCHK(hipGetLastError());
     }
-    return diag_combine(ctx, m, 3, out);
+    return diag_combine<DiagSum<3>>(ctx, m, out);
 }
 
 int knp_diag_set_facet_tags(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr, const int32_t* facets) {
     CHECK_CTX(ctx);
-    return diag_map_set(ctx, ctx->diag_facets, n_tags, seg_ptr, facets, ctx->g.n_g, DIAG_BT, 1, "facet tag map");
+    return diag_map_set(ctx, ctx->diag_facets, n_tags, seg_ptr, facets, ctx->g.n_g, DIAG_BT, 1, 0, "facet tag map");
 }
 
 int knp_diag_set_program(knp_ctx* ctx, int32_t n_instr, const int32_t* code, int32_t n_consts, const double* consts) {
@@ -533,9 +539,8 @@ int knp_diag_set_program_constants(knp_ctx* ctx, int32_t n_consts, const double*
 int knp_diag_membrane_integral(knp_ctx* ctx, const knp_fields* fields, double* out) {
     CHECK_CTX(ctx);
     KCHK(check_fields(ctx, fields, true));
-    if (!out) { ctx->err = "null output buffer"; return KNP_E_ARG; }
     const KnpDiagMap& m = ctx->diag_facets;
-    if (!m.d_ptr) { ctx->err = "no facet tag map (knp_diag_set_facet_tags)"; return KNP_E_STATE; }
+    KCHK(diag_check(ctx, out, m.d_ptr, "no facet tag map (knp_diag_set_facet_tags)"));
     if (!ctx->diag_prog) { ctx->err = "no diagnostic program (knp_diag_set_program)"; return KNP_E_STATE; }
     int n_aux = 0;
     for (int k = 0; k < KNP_MAX_AUX; ++k)
@@ -548,17 +553,14 @@ int knp_diag_membrane_integral(knp_ctx* ctx, const knp_fields* fields, double* o
         for (int i = 0; i < KNP_DIAG_MAX_CONSTS; ++i) K.v[i] = i < ctx->diag_n_consts ? ctx->diag_consts[i] : 0.0;
         const size_t lds = (size_t)std::max(ctx->diag_n_regs, 1) * DIAG_BT * sizeof(double);   // <= 48 registers: 48 KiB
         const int n_q = ctx->g.n_q;
-        if (ctx->g.dim == 2)
-            hipLaunchKernelGGL(k_diag_facets<2>, dim3(m.n_chunks), dim3(DIAG_BT), lds, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_fv,
+        by_dim(ctx->g.dim, [&](auto D) {
+            hipLaunchKernelGGL(k_diag_facets<D()>, dim3(m.n_chunks), dim3(DIAG_BT), lds, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_fv,
                                ctx->d_fmeas, n_q, ctx->d_qp, ctx->d_qw, f, n_aux, ctx->d_coords, ctx->diag_code, ctx->diag_n_instr, K,
                                ctx->diag_n_consts, m.d_partial);
-        else
-            hipLaunchKernelGGL(k_diag_facets<3>, dim3(m.n_chunks), dim3(DIAG_BT), lds, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_fv,
-                               ctx->d_fmeas, n_q, ctx->d_qp, ctx->d_qw, f, n_aux, ctx->d_coords, ctx->diag_code, ctx->diag_n_instr, K,
-                               ctx->diag_n_consts, m.d_partial);
+        });
         HIPCHK(hipGetLastError());
     }
-    return diag_combine(ctx, m, 1, out);
+    return diag_combine<DiagSum<1>>(ctx, m, out);
 }
 
 int knp_diag_set_flux_facets(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr, const int32_t* facets, const double* box_lo,
@@ -566,7 +568,7 @@ int knp_diag_set_flux_facets(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_pt
     CHECK_CTX(ctx);
     if ((box_lo == nullptr) != (box_hi == nullptr)) { ctx->err = "flux facet map: box_lo and box_hi must both be given or both be null"; return KNP_E_ARG; }
     const KnpHostGraph& g = ctx->g;
-    KCHK(diag_map_set(ctx, ctx->diag_flux, n_tags, seg_ptr, facets, g.n_g, NT, 6, "flux facet map"));
+    KCHK(diag_map_set(ctx, ctx->diag_flux, n_tags, seg_ptr, facets, g.n_g, NT, 6, 0, "flux facet map"));
     dev_free(ctx->d_flux_rec);
     const int n = ctx->diag_flux.n;
     std::vector<double> coords((size_t)g.n_v * g.dim), qp((size_t)g.n_q * g.dim), qw((size_t)g.n_q);
@@ -579,8 +581,7 @@ int knp_diag_set_flux_facets(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_pt
         rc = KNP_E_HIP;
     }
     if (rc == KNP_OK)
-        rc = g.dim == 2 ? flux_records<2>(ctx, facets, n, coords, qp.data(), qw.data(), box_lo, box_hi, rec)
-                        : flux_records<3>(ctx, facets, n, coords, qp.data(), qw.data(), box_lo, box_hi, rec);
+        rc = by_dim(g.dim, [&](auto D) { return flux_records<D()>(ctx, facets, n, coords, qp.data(), qw.data(), box_lo, box_hi, rec); });
     if (rc == KNP_OK) rc = dev_upload(ctx, &ctx->d_flux_rec, rec);
     if (rc != KNP_OK) {     // no half-set map: the next knp_diag_membrane_fluxes reports KNP_E_STATE
         diag_map_free(ctx->diag_flux);
@@ -597,69 +598,40 @@ int knp_diag_membrane_fluxes(knp_ctx* ctx, const knp_fields* fields, const doubl
         if (!fields->k_i[j] || !fields->k_e[j]) { ctx->err = "null concentration field"; return KNP_E_ARG; }
     if (!phi_i || !phi_e) { ctx->err = "null potential field (phi_i / phi_e)"; return KNP_E_ARG; }
     if (!D || !z_over_psi) { ctx->err = "null flux coefficients (D / z_over_psi)"; return KNP_E_ARG; }
-    if (!out) { ctx->err = "null output buffer"; return KNP_E_ARG; }
     const KnpDiagMap& m = ctx->diag_flux;
-    if (!m.d_ptr || !ctx->d_flux_rec) { ctx->err = "no flux facet map (knp_diag_set_flux_facets)"; return KNP_E_STATE; }
+    KCHK(diag_check(ctx, out, m.d_ptr && ctx->d_flux_rec, "no flux facet map (knp_diag_set_flux_facets)"));
     if (m.n > 0) {
         const FieldPtrs f = make_fields(fields);
         FluxCoef K;
         for (int j = 0; j < 3; ++j) { K.D[j] = D[j]; K.zp[j] = z_over_psi[j]; }
-        if (ctx->g.dim == 2)
-            hipLaunchKernelGGL(k_diag_fluxes<2>, dim3(m.n_chunks), dim3(NT), 0, ctx->stream, m.n, m.d_key, ctx->d_flux_rec, f, phi_i, phi_e, K,
+        by_dim(ctx->g.dim, [&](auto D) {
+            hipLaunchKernelGGL(k_diag_fluxes<D()>, dim3(m.n_chunks), dim3(NT), 0, ctx->stream, m.n, m.d_key, ctx->d_flux_rec, f, phi_i, phi_e, K,
                                m.d_partial);
-        else
-            hipLaunchKernelGGL(k_diag_fluxes<3>, dim3(m.n_chunks), dim3(NT), 0, ctx->stream, m.n, m.d_key, ctx->d_flux_rec, f, phi_i, phi_e, K,
-                               m.d_partial);
+        });
         HIPCHK(hipGetLastError());
     }
-    return diag_combine(ctx, m, 6, out);
+    return diag_combine<DiagSum<6>>(ctx, m, out);
 }
 
+static constexpr int PHIM_WAVE_CHUNKS = 64;      // longer tags take the workgroup combine
 int knp_diag_set_phim_facets(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr, const int32_t* facets) {
     CHECK_CTX(ctx);
-    KCHK(diag_map_set(ctx, ctx->diag_phim, n_tags, seg_ptr, facets, ctx->g.n_g, DIAG_BT, 3, "phi_m facet map"));
-    dev_free(ctx->d_phim_long);
-    ctx->n_phim_long = 0;
-    std::vector<int32_t> lng;             // the tags the workgroup combine takes: by chunk count alone
-    for (int s = 0; s < n_tags; ++s)
-        if (seg_ptr[s + 1] > seg_ptr[s] && (seg_ptr[s + 1] - 1) / DIAG_BT - seg_ptr[s] / DIAG_BT + 1 > PHIM_WAVE_CHUNKS) lng.push_back(s);
-    if (!lng.empty()) {
-        const int rc = dev_upload(ctx, &ctx->d_phim_long, lng);
-        if (rc != KNP_OK) {               // no half-set map
-            diag_map_free(ctx->diag_phim);
-            dev_free(ctx->d_phim_long);
-            return rc;
-        }
-        ctx->n_phim_long = (int)lng.size();
-    }
-    return KNP_OK;
+    return diag_map_set(ctx, ctx->diag_phim, n_tags, seg_ptr, facets, ctx->g.n_g, DIAG_BT, 3, PHIM_WAVE_CHUNKS, "phi_m facet map");
 }
 
 int knp_diag_membrane_potential(knp_ctx* ctx, const knp_fields* fields, double* out) {
     CHECK_CTX(ctx);
     if (!fields || !fields->phi_m) { ctx->err = "null fields or null phi_m field"; return KNP_E_ARG; }
-    if (!out) { ctx->err = "null output buffer"; return KNP_E_ARG; }
     const KnpDiagMap& m = ctx->diag_phim;
-    if (!m.d_ptr) { ctx->err = "no phi_m facet map (knp_diag_set_phim_facets)"; return KNP_E_STATE; }
-    if (m.n_tags == 0) return KNP_OK;
+    KCHK(diag_check(ctx, out, m.d_ptr, "no phi_m facet map (knp_diag_set_phim_facets)"));
     if (m.n > 0) {
-        if (ctx->g.dim == 2)
-            hipLaunchKernelGGL(k_diag_phim<2>, dim3(m.n_chunks), dim3(DIAG_BT), 0, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_fv,
+        by_dim(ctx->g.dim, [&](auto D) {
+            hipLaunchKernelGGL(k_diag_phim<D()>, dim3(m.n_chunks), dim3(DIAG_BT), 0, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_fv,
                                ctx->d_fmeas, fields->phi_m, m.d_partial);
-        else
-            hipLaunchKernelGGL(k_diag_phim<3>, dim3(m.n_chunks), dim3(DIAG_BT), 0, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_fv,
-                               ctx->d_fmeas, fields->phi_m, m.d_partial);
+        });
         HIPCHK(hipGetLastError());
     }
-    const unsigned nb = (unsigned)((m.n_tags + NT / 64 - 1) / (NT / 64));
-    hipLaunchKernelGGL(k_diag_phim_combine, dim3(nb), dim3(NT), 0, ctx->stream, m.n_tags, m.chunk, m.d_ptr, m.d_partial, out);
-    HIPCHK(hipGetLastError());
-    if (ctx->n_phim_long > 0) {
-        hipLaunchKernelGGL(k_diag_phim_combine_long, dim3(ctx->n_phim_long), dim3(NT), 0, ctx->stream, ctx->d_phim_long, m.chunk, m.d_ptr,
-                           m.d_partial, out);
-        HIPCHK(hipGetLastError());
-    }
-    return KNP_OK;
+    return diag_combine<DiagPhim>(ctx, m, out);
 }
 
 }  // extern "C"

@@ -65,10 +65,13 @@ void knp_diag_free(knp_ctx* ctx);
 // ---- tag map of a diagnostic reduction (knp_diagnostics.inc): items sorted by dense tag index --------------------------------
 struct KnpDiagMap {
     int n_tags = 0, n = 0, chunk = 0, n_chunks = 0;
+    int wave_chunks = 0;           // > 0: tags of more chunks than this go to the workgroup combine; 0: the wave combine takes all
     int32_t* d_ptr = nullptr;      // [n_tags+1] segment offsets
     int32_t* d_item = nullptr;     // [n] cell / facet ids, sorted by tag
     int32_t* d_key = nullptr;      // [n] tag index of every item
     double* d_partial = nullptr;   // [(n_tags + n_chunks) * values] per (chunk, tag) partial sums
+    int32_t* d_long = nullptr;     // [n_long] the tags of the workgroup combine
+    int n_long = 0;
 };
 
 // ---- device-side program ------------------------------------------------------------------
@@ -377,10 +380,8 @@ struct knp_ctx {
     // trans-membrane ion fluxes (knp_diag_set_flux_facets): a tag map of its own and one time-invariant record per listed facet, in map order
     KnpDiagMap diag_flux;
     double2* d_flux_rec = nullptr;   // [diag_flux.n * (dim == 3 ? 8 : 7)] 16-byte units, layout at k_diag_fluxes
-    // membrane potential per tag (knp_diag_set_phim_facets): a tag map of its own and the tags whose partials a whole workgroup combines
+    // membrane potential per tag (knp_diag_set_phim_facets): a tag map of its own
     KnpDiagMap diag_phim;
-    int32_t* d_phim_long = nullptr;  // [n_phim_long] tags spanning more than 64 chunks
-    int n_phim_long = 0;
     int32_t* diag_code = nullptr;
     int diag_n_instr = 0, diag_n_regs = 0, diag_n_consts = 0;
     double diag_consts[KNP_DIAG_MAX_CONSTS] = {};   // host copy: passed to the kernel by value at every launch

@@ -89,6 +89,22 @@ def test_random_fields_match_the_reference_per_tag_side_and_ion(case):
     assert be.membrane_fluxes().cpu().numpy().tobytes() == got.tobytes()
 
 
+def test_one_group_of_94_chunks_matches_the_reference():
+    """more chunks than the 64 lanes of the combine's wave: its lanes fold several partials each before the butterfly"""
+    p = make_problem(tissue_config(3, 30, 5, steps=1), "ci")
+    be = p.create_backend()
+    _random_fields(p, 11)
+    tags = [int(t) for t in p.gamma_tags]
+    assert len(tags) == 125
+    be.set_flux_groups([tags])
+    got = be.membrane_fluxes().cpu().numpy()
+    ref, S, cover = _reference(p, [tags], False)
+    assert got.shape == (1, 2, 3) and len(cover[0]) == 24000 and (24000 - 1) // 256 + 1 == 94
+    assert np.all(S > 0) and np.all(np.abs(ref) > 0)
+    assert _close(got, ref, S)
+    assert be.membrane_fluxes().cpu().numpy().tobytes() == got.tobytes()
+
+
 # ---- 2. affine fields: the divergence theorem per closed cell membrane, volumes from the budget kernel --------------------------
 @pytest.mark.parametrize("dim,N,m", [(2, 18, 3), (3, 12, 2)])
 def test_affine_fields_give_the_cell_volume_times_the_mixed_term(dim, N, m):

@@ -162,6 +162,54 @@ def _host_stimulus(p):
     return float((fm[:, None] * vals * p.q_w[None, :]).sum())
 
 
+@pytest.fixture(scope="module")
+def long_tags():
+    """tissue_config(3, 30, 5) with random fields and no time step: tags of more chunks than the 64 lanes of the combine's wave"""
+    import torch
+    p = make_problem(tissue_config(3, 30, 5, steps=1), "ci")
+    be = p.create_backend()
+    rng = np.random.default_rng(29)
+    n = p.local_mesh.coords.shape[0]
+    write = lambda fn, v: fn.x.array.copy_(torch.from_numpy(v).to(fn.x.array.device))
+    for s in range(2):
+        for j in range(p.N_ions):
+            write(p.wh[s][j], rng.uniform(1.0, 150.0, n))
+        write(p.wh[s][p.N_ions], rng.uniform(-0.1, 0.1, n))
+    write(p.phi_m_prev, p.wh[0][p.N_ions].numpy() - p.wh[1][p.N_ions].numpy())
+    return p, be
+
+
+def test_ion_amounts_of_a_tag_longer_than_a_wave_match_host_integrals(long_tags):
+    p, be = long_tags
+    lay = be.budget_layout()
+    tags, host = _host_budget(p)
+    assert np.array_equal(lay.tags, tags)
+    e = len(tags) - 1                                         # the extracellular tag
+    assert lay.side[e] == 1
+    chunks = (lay.seg_ptr[e + 1] - 1) // 256 - lay.seg_ptr[e] // 256 + 1
+    print("extracellular tag:", lay.seg_ptr[e + 1] - lay.seg_ptr[e], "cells in", chunks, "chunks")
+    assert chunks > 64
+    got = be.ion_amounts().cpu().numpy()
+    print("max rel. difference", np.abs(got / host - 1.0).max())
+    assert np.allclose(got, host, rtol=1e-12, atol=0)
+    assert be.ion_amounts().cpu().numpy().tobytes() == got.tobytes()
+
+
+def test_membrane_integral_of_a_group_longer_than_a_wave_matches_host_quadrature(long_tags):
+    import torch
+    from cgx_hip.diagnostics import facet_group_map, membrane_program
+    p, be = long_tags
+    seg_ptr, facets = facet_group_map(p, [p.stimulus_tags])
+    assert len(facets) == 24000 and (seg_ptr[1] - 1) // 128 + 1 == 188      # one group, 188 chunks of 128
+    be.set_diag_program(membrane_program(p, p.stim_ufl_expr))
+    be.set_facet_groups([p.stimulus_tags])
+    got = be.membrane_integral(torch.zeros(1, dtype=torch.float64, device=be.device)).cpu().numpy()
+    host = np.array([_host_stimulus(p)])
+    print("device", got[0], "host", host[0], "rel. difference", abs(got[0] / host[0] - 1.0))
+    assert np.abs(host).max() > 0
+    assert np.allclose(got, host, rtol=1e-12, atol=1e-12 * np.abs(host).max())
+
+
 def _write_cfg(tmp_path, name, cfg, out_dir):
     cfg = copy.deepcopy(cfg)
     cfg["output_dir"] = str(out_dir) + "/"

@@ -4,7 +4,7 @@ integral on the facet map of one tissue surrogate, without a solve.  Meant to ru
     python tools/phim_trace_run.py run <dim> <N> <m> [--width W] [--reps R]
         phase 1, one group per membrane tag: 1 + R times membrane_potential() and membrane_fluxes()
         phase 2, all tags merged into one group: 1 + R times membrane_potential(), membrane_fluxes() and membrane_integral()
-        (k_diag_facets + the one-wave k_diag_combine<1> of the stimulus trace)
+        (k_diag_facets + the one-wave k_diag_combine<DiagSum<1>> of the stimulus trace)
     python tools/phim_trace_run.py summarise <kernel_trace.csv> [--reps R]
         per phase and diagnostics kernel: calls, average / min / max ns over the R launches after each phase's first one, as CSV
 
@@ -31,9 +31,9 @@ s.add_argument("trace")
 s.add_argument("--reps", type=int, default=5)
 a = ap.parse_args()
 
-KERNELS = ("k_diag_phim<", "k_diag_phim_combine_long", "k_diag_phim_combine(", "k_diag_fluxes<", "k_diag_combine<6>", "k_diag_facets<",
-           "k_diag_combine<1>")
-MERGED_ONLY = ("k_diag_phim_combine_long", "k_diag_facets<", "k_diag_combine<1>")
+KERNELS = ("k_diag_phim<", "k_diag_combine_long<DiagPhim>", "k_diag_combine<DiagPhim>", "k_diag_fluxes<", "k_diag_combine<DiagSum<6>", "k_diag_facets<",
+           "k_diag_combine<DiagSum<1>")
+MERGED_ONLY = ("k_diag_combine_long<DiagPhim>", "k_diag_facets<", "k_diag_combine<DiagSum<1>")
 
 if a.cmd == "summarise":
     rows = []
