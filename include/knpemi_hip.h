@@ -38,6 +38,8 @@
  *   knp_diag_set_phim_facets / knp_diag_membrane_potential
  *        integral, minimum and maximum of phi_m per membrane tag: what utils/plot_membrane_potentials.py:48-128 reads per cell from
  *        the reference's per-step checkpoints
+ *   knp_emi_*                        the EMI model (src/CGx/EMI): assemble_matrix_block / assemble_vector_block of the forms
+ *                                    EMIx_problem.py:152-157, 215-217 and ksp.solve with KSPCG (EMIx_solver.py)
  *   knp_set_comm                     the MPI calls hidden in PETSc/DOLFINx (ghost updates
  *                                    KNPEMIx_solver.py:439,459,468; Allreduce inside KSPSolve)
  *
@@ -154,7 +156,8 @@ enum {
     KNP_SZ_N_NODES = 0, KNP_SZ_N_NODES_OWNED = 1, KNP_SZ_N_DOF_LOCAL = 2, KNP_SZ_N_DOF_OWNED = 3,
     KNP_SZ_NNZ = 4, KNP_SZ_N_PAIRS = 5, KNP_SZ_N_CONTRIB = 6, KNP_SZ_N_GAMMA_VERTS = 7,
     KNP_SZ_N_GAMMA_PAIRS = 8, KNP_SZ_NNZ_P = 9, KNP_SZ_N_PHI_OWNED = 10,
-    KNP_SZ_NNZ_P_PHI = 11 /* entries of knp_get_precond_phi_csr */, KNP_SZ_COUNT = 16
+    KNP_SZ_NNZ_P_PHI = 11 /* entries of knp_get_precond_phi_csr */, KNP_SZ_EMI_NNZ = 12 /* entries of knp_emi_get_csr, 0 before knp_emi_setup */,
+    KNP_SZ_COUNT = 16
 };
 
 /* communication hooks (multi-GPU); both receive DEVICE pointers */
@@ -405,6 +408,50 @@ int knp_diag_membrane_fluxes(knp_ctx* ctx, const knp_fields* fields, const doubl
 int knp_diag_set_phim_facets(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr /* host [n_tags+1] */,
                              const int32_t* facets /* host [seg_ptr[n_tags]] */);
 int knp_diag_membrane_potential(knp_ctx* ctx, const knp_fields* fields, double* out /* device [n_tags*3] */);
+
+/* ---- the EMI model: two potentials with constant conductivities, ONE unknown per node (reference src/CGx/EMI) ----
+ * Unknown n is node n of knp_get_layout; every vector is a device array of n_nodes_owned doubles.  One GPU only: every call
+ * returns KNP_E_STATE on a context with ghost nodes, and -- knp_emi_setup apart -- before knp_emi_setup; KNP_E_ARG for a null argument.
+ *   A = [ dt sigma_i K_i + C_M M_Gamma     -C_M M_Gamma              ]   (EMIx_problem.py:152-157)
+ *       [ -C_M M_Gamma                     dt sigma_e K_e + C_M M_Gamma ]
+ * symmetric positive semi-definite, constant in time.  Pure Neumann: A 1 = 0 over ALL nodes (knp_set_nullspace(ctx, 1) declares it).
+ * knp_emi_setup: a kernel writes one value per same-side node pair and one per membrane vertex pair (the entry towards the other
+ *   side's node) from the graph of knp_create, and the inverse diagonal.  Calling it again rewrites the values (another dt); an
+ *   uploaded hierarchy is then stale.  After it, knp_amg_set_level takes n_nodes_owned rows on level 0 (and refuses n_dof_owned).
+ * knp_emi_get_csr: A as CSR, rows / columns = nodes: row n = its same-side pairs in the order of the node graph (columns ascending),
+ *   then, for a membrane vertex, the entries towards the other side.  KNP_SZ_EMI_NNZ entries.  Dirichlet nodes are NOT applied.
+ * knp_emi_set_dirichlet: the listed nodes become identity rows AND columns of the operator knp_emi_spmv, knp_emi_pc_apply and
+ *   knp_emi_cg_solve work with (symmetric elimination); n = 0 clears.  Host array, copied.
+ * knp_emi_spmv: y = A x (with the Dirichlet elimination).
+ * knp_emi_assemble_rhs: b_i = dt M_i f_i + s int_Gamma (C_M phi_m - dt I_ch) v dS, b_e = dt M_e f_e - s (the same), s = rhs_scale.
+ *   phi_m = fields->phi_m and the gating variables fields->aux are nodal [n_vertices] and interpolated to the n_q points of the
+ *   facet rule; I_ch is the sum of the outputs of the facet's membrane program (knp_set_program, bytecode interpreter; KNP_OP_KI /
+ *   KNP_OP_KE read 0; no run-time compiled kernel is built on a context that assembles EMI right-hand sides).  fields->k_i / k_e are not read.  f_i, f_e: nodal [n_vertices], NULL = 0.  g: [n_nodes_owned] or NULL; with
+ *   Dirichlet nodes b -= A g on the other rows and b = g on the Dirichlet ones.  With the null space on, b is projected at the end.
+ *   Gathers per node, no atomics.
+ * knp_emi_pc_setup / knp_emi_pc_apply: KNP_PC_NONE, KNP_PC_VBJACOBI (point Jacobi here) or KNP_PC_AMG: the generic level-by-level
+ *   V-cycle on hierarchy 0, uploaded with knp_amg_reset / knp_amg_set_level / knp_amg_set_coarse after knp_emi_setup, level 0 = A
+ *   (with the Dirichlet elimination).  pre == post sweeps keep it symmetric.  knp_emi_pc_apply projects z when the null space is on.
+ * knp_emi_cg_solve: preconditioned conjugate gradients with PETSc's KSPCG semantics.  x on entry is the initial guess.  norm_type
+ *   0 preconditioned ||B r||_2 (KSPCG's default), 1 unpreconditioned ||r||_2, 2 natural sqrt(r . B r).  Stops when the norm is
+ *   <= max(rtol * (the same norm of b), atol); reason codes and the divergence test (1e5 times that reference) as knp_gmres_solve;
+ *   p . A p <= 0, a non-finite value or a preconditioned norm lost to
+ *   cancellation (null space on, B r constant to 8 digits) ends it with KNP_DIVERGED_NANORINF.  alpha and beta stay on the device, the reductions are
+ *   two-stage in a fixed order (the same bits on every run), one pinned read-back per iteration.  With the null space on B's output
+ *   is projected, so the component of x along the constant is that of the initial guess.  Dirichlet nodes: x = b there on return,
+ *   exactly (set before the first residual).
+ * knp_emi_update: phi_i / phi_e [n_vertices] = x at the vertex's intra / extra node, 0 where it has none; phi_m = phi_i - phi_e. */
+int knp_emi_setup(knp_ctx* ctx, double dt, double C_M, double sigma_i, double sigma_e);
+int knp_emi_get_csr(knp_ctx* ctx, int32_t* rowptr /* host [n_nodes_owned + 1] */, int32_t* colind, double* vals /* host [KNP_SZ_EMI_NNZ] */);
+int knp_emi_set_dirichlet(knp_ctx* ctx, int32_t n, const int32_t* nodes /* host */);
+int knp_emi_spmv(knp_ctx* ctx, const double* x, double* y);
+int knp_emi_assemble_rhs(knp_ctx* ctx, const knp_fields* fields, const double* f_i, const double* f_e, const double* g,
+                         double rhs_scale, double* b);
+int knp_emi_pc_setup(knp_ctx* ctx, int32_t kind);
+int knp_emi_pc_apply(knp_ctx* ctx, const double* r, double* z);
+int knp_emi_cg_solve(knp_ctx* ctx, const double* b, double* x, double rtol, double atol, int32_t max_it, int32_t norm_type,
+                     int32_t* its, double* rnorm, int32_t* reason);
+int knp_emi_update(knp_ctx* ctx, const double* x, double* phi_i, double* phi_e, double* phi_m);
 
 /* ---- instrumentation ---- */
 /* elapsed ms and launch count of a kernel class since the last reset (HIP events on the ctx stream).

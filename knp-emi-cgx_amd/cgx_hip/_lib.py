@@ -17,7 +17,7 @@ KNP_MAX_PROG_REGS = 48
 KNP_DIAG_MAX_CONSTS = 64
 KNP_SZ_COUNT = 16
 (SZ_N_NODES, SZ_N_NODES_OWNED, SZ_N_DOF_LOCAL, SZ_N_DOF_OWNED, SZ_NNZ, SZ_N_PAIRS, SZ_N_CONTRIB,
- SZ_N_GAMMA_VERTS, SZ_N_GAMMA_PAIRS, SZ_NNZ_P, SZ_N_PHI_OWNED, SZ_NNZ_P_PHI) = range(12)
+ SZ_N_GAMMA_VERTS, SZ_N_GAMMA_PAIRS, SZ_NNZ_P, SZ_N_PHI_OWNED, SZ_NNZ_P_PHI, SZ_EMI_NNZ) = range(13)
 
 PC_NONE, PC_VBJACOBI, PC_AMG, PC_AMG_BT, PC_AMG_LT = 0, 1, 2, 3, 4
 
@@ -128,6 +128,15 @@ SIGNATURES = {
     "knp_diag_membrane_fluxes": (C.c_int, [vp, C.POINTER(Fields), vp, vp, f64p, f64p, vp]),
     "knp_diag_set_phim_facets": (C.c_int, [vp, C.c_int32, i32p, i32p]),
     "knp_diag_membrane_potential": (C.c_int, [vp, C.POINTER(Fields), vp]),
+    "knp_emi_setup": (C.c_int, [vp, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "knp_emi_get_csr": (C.c_int, [vp, i32p, i32p, f64p]),
+    "knp_emi_set_dirichlet": (C.c_int, [vp, C.c_int32, i32p]),
+    "knp_emi_spmv": (C.c_int, [vp, vp, vp]),
+    "knp_emi_assemble_rhs": (C.c_int, [vp, C.POINTER(Fields), vp, vp, vp, C.c_double, vp]),
+    "knp_emi_pc_setup": (C.c_int, [vp, C.c_int32]),
+    "knp_emi_pc_apply": (C.c_int, [vp, vp, vp]),
+    "knp_emi_cg_solve": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_int32, C.c_int32, i32p, f64p, i32p]),
+    "knp_emi_update": (C.c_int, [vp, vp, vp, vp, vp]),
     "knp_timer_mark": (C.c_int, [vp, C.c_int32]),
     "knp_timer_read": (C.c_int, [vp, C.c_int32, f64p, C.POINTER(C.c_int32)]),
     "knp_timer_pending": (C.c_int, [vp]),

@@ -61,6 +61,23 @@ struct knp_ctx;
 void knp_jit_build(knp_ctx* ctx);
 void knp_jit_release(knp_ctx* ctx);
 void knp_diag_free(knp_ctx* ctx);
+void knp_emi_free(knp_ctx* ctx);
+
+// ---- the EMI model (knp_emi.inc): one unknown per node on the graph knp_create built ------------------------------------------
+struct KnpEmi {
+    bool ready = false;              // knp_emi_setup has run
+    double dt = 0, C_M = 0, sigma_i = 0, sigma_e = 0;
+    double* d_val = nullptr;         // [n_pairs] dt sigma_side K (+ C_M M_Gamma between membrane vertices), in the order of pair_col
+    double* d_xval = nullptr;        // [n_gp] -C_M M_Gamma: the entry towards the other side's node of every membrane vertex pair
+    double* d_dinv = nullptr;        // [n_nodes_owned] inverse diagonal (1 on Dirichlet nodes)
+    uint8_t* d_mask = nullptr;       // [n_nodes_owned] 1 = Dirichlet node
+    int n_bc = 0;
+    int pc_kind = 0;                 // KNP_PC_NONE, KNP_PC_VBJACOBI (point Jacobi here), KNP_PC_AMG
+    double *d_r = nullptr, *d_z = nullptr, *d_p = nullptr, *d_q = nullptr, *d_t = nullptr;   // CG work vectors [n_nodes_owned]
+    double* d_fvec = nullptr;        // [dim * n_g] membrane integral of every facet against each of its vertices' hat functions
+    int aux_need = -1;               // highest aux field + 1 that a membrane program reads; -1: the program table is not built yet
+    double* d_st = nullptr;          // [4] CG scalars on the device: r.z of the previous / current iteration (ping-pong), breakdown flag
+};
 
 // ---- tag map of a diagnostic reduction (knp_diagnostics.inc): items sorted by dense tag index --------------------------------
 struct KnpDiagMap {
@@ -386,6 +403,7 @@ struct knp_ctx {
     int diag_n_instr = 0, diag_n_regs = 0, diag_n_consts = 0;
     double diag_consts[KNP_DIAG_MAX_CONSTS] = {};   // host copy: passed to the kernel by value at every launch
     bool diag_prog = false;
+    KnpEmi emi;
     // profiling
     int prof_on = 0;
     std::vector<hipEvent_t> prof_pool;   // recycled timing events

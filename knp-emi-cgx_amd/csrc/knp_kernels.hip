@@ -3109,6 +3109,7 @@ int knp_destroy(knp_ctx* ctx) {
     dev_free(ctx->d_ML); dev_free(ctx->d_cc); dev_free(ctx->d_t2); dev_free(ctx->d_w2);
     dev_free(ctx->d_defl_mode); dev_free(ctx->d_defl_einv); dev_free(ctx->d_bc_dofs);
     knp_diag_free(ctx);
+    knp_emi_free(ctx);
     delete ctx;
     return KNP_OK;
 }
@@ -3140,6 +3141,7 @@ int knp_get_sizes(const knp_ctx* ctx, int64_t* s) {
     s[KNP_SZ_NNZ_P] = 4 * ctx->n_pairs;
     s[KNP_SZ_N_PHI_OWNED] = ctx->g.n_nodes_owned;
     s[KNP_SZ_NNZ_P_PHI] = phi_block_nnz(ctx);
+    s[KNP_SZ_EMI_NNZ] = ctx->emi.ready ? ctx->n_pairs + 2 * ctx->n_gp : 0;
     return KNP_OK;
 }
 int knp_get_layout(const knp_ctx* ctx, int32_t* ni, int32_t* ne) {
@@ -3985,7 +3987,11 @@ int knp_amg_set_level(knp_ctx* ctx, int32_t hier, int32_t level, int32_t n_rows,
     if (hier < 0 || hier >= KNP_MAX_HIER) { ctx->err = "bad hierarchy index"; return KNP_E_ARG; }
     KnpAmgHier& H = ctx->hier[hier];
     if (level < 0 || level >= H.levels || n_rows <= 0 || !A_rp || !A_ci || !A_v || !inv_diag) { ctx->err = "bad AMG level arguments"; return KNP_E_ARG; }
-    if (level == 0 && n_rows != ctx->n_dof_owned) { ctx->err = "AMG level 0 must have n_dof_owned rows"; return KNP_E_ARG; }
+    // an EMI context (knp_emi_setup has run) has one unknown per node: its hierarchy starts on the EMI matrix
+    if (level == 0 && n_rows != (ctx->emi.ready ? ctx->g.n_nodes_owned : ctx->n_dof_owned)) {
+        ctx->err = ctx->emi.ready ? "AMG level 0 of an EMI context must have n_nodes_owned rows" : "AMG level 0 must have n_dof_owned rows";
+        return KNP_E_ARG;
+    }
     KnpAmgLevel& L = H.lv[level];
     const int64_t nnzA = A_rp[n_rows];
     const int n_loc = std::max(n_cols_halo, n_rows);
@@ -5052,3 +5058,6 @@ int knp_get_stats(const knp_ctx* ctx, double* out) {
 
 // per-tag diagnostics: ion amounts per cell tag, membrane integrals of one program (knp_diag_*)
 #include "knp_diagnostics.inc"
+
+// the EMI model: scalar matrix on the node graph, membrane right-hand side, preconditioned conjugate gradients (knp_emi_*)
+#include "knp_emi.inc"
