@@ -481,6 +481,19 @@ int knp_get_stats(const knp_ctx* ctx, double* out /* host [KNP_ST_COUNT] */);
 /* bytes the kernels of one application must move, from the sizes of the arrays they read and write (per-class roofline): [0] SpMV on A,
  * [1] one preconditioner application, [2] matrix assembly of one step, [3] right-hand side assembly, [4] one owned vector */
 int knp_get_traffic_model(const knp_ctx* ctx, double* out /* host [5] */);
+/* which kernels the context launches, from the choices made at creation (context fields only; nothing is launched): the first
+ * min(n, KNP_LI_COUNT) slots are written.  KNP_E_ARG for a null argument or n <= 0.  The knp_emi_* kernels run 8 lanes per node whatever
+ * the groups say; of these fields the graph sizes (MAX_NODE_CELLS, MAX_NODE_PAIRS) are what bears on them. */
+enum { KNP_LI_ASM_VARIANT = 0 /* volume assembly: 0 plain gather, 1 staged with pair-major lists, 2 staged with transposed lists */,
+       KNP_LI_ASM_STAGE = 1 /* LDS slots for cell means per node (0: not staged) */,
+       KNP_LI_ASM_DMAX = 2 /* > 0: cell means fused into the assembly, LDS slots for this many neighbours per node */,
+       KNP_LI_ASM_GROUP = 3, KNP_LI_SPMV_GROUP = 4, KNP_LI_PC_GROUP = 5 /* lanes per node: assembly, SpMV, level-0 preconditioner */,
+       KNP_LI_MAX_NODE_CELLS = 6 /* most same-side cells around an owned node */,
+       KNP_LI_MAX_NODE_PAIRS = 7 /* most node pairs of an owned node (its row of the node graph, self pair included) */,
+       KNP_LI_SPMV_UNROLL = 8 /* pairs in flight per lane of the SpMV on A (KNP_SPMV_UNROLL, read once per process) */,
+       KNP_LI_SPMV_MK = 9 /* 1: the SpMV on A reads {M, K} per pair, 0: the stored time-invariant entries (Dirichlet rows, KNP_SPMV_MF=0) */,
+       KNP_LI_COUNT = 10 };
+int knp_get_launch_info(const knp_ctx* ctx, int32_t* out /* host [n] */, int n);
 
 #ifdef __cplusplus
 }

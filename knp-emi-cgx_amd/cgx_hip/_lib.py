@@ -145,6 +145,7 @@ SIGNATURES = {
     "knp_profile_reset": (C.c_int, [vp]),
     "knp_get_stats": (C.c_int, [vp, f64p]),
     "knp_get_traffic_model": (C.c_int, [vp, f64p]),
+    "knp_get_launch_info": (C.c_int, [vp, i32p, C.c_int]),
 }
 
 _lib = None

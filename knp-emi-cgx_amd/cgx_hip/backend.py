@@ -728,6 +728,14 @@ class Backend:
         self.check(self.lib.knp_get_traffic_model(self.ctx, out))
         return {"spmv": out[0], "pc": out[1], "assembly_matrix": out[2], "assembly_rhs": out[3], "vector": out[4]}
 
+    def launch_info(self):
+        """which kernels this context launches: the choices ``knp_create`` made (knp_get_launch_info; nothing is launched)"""
+        names = ["asm_variant", "asm_stage", "asm_dmax", "asm_group", "spmv_group", "pc_group", "max_node_cells", "max_node_pairs",
+                 "spmv_unroll", "spmv_mk"]
+        out = (C.c_int32 * len(names))()      # KNP_LI_COUNT
+        self.check(self.lib.knp_get_launch_info(self.ctx, out, len(names)))
+        return dict(zip(names, (int(v) for v in out)))
+
     def profile_get(self):
         names = ["spmv", "orthogonalisation", "pc", "assembly", "other"]
         out = {}

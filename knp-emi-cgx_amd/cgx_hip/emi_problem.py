@@ -186,6 +186,12 @@ class EmiBackend:
         self.check(self.lib.knp_timer_read(self.ctx, max(n, 1), out, C.byref(k)))
         return np.array(out[:k.value], dtype=np.float64)
 
+    def launch_info(self):
+        """the fields of ``knp_get_launch_info`` that bear on the EMI kernels (8 lanes per node, fixed): the graph sizes"""
+        out = (C.c_int32 * 10)()      # KNP_LI_COUNT
+        self.check(self.lib.knp_get_launch_info(self.ctx, out, 10))
+        return {"max_node_cells": int(out[6]), "max_node_pairs": int(out[7]), "emi_group": 8}
+
     # ---- export
     def csr(self, eliminated=False):
         """the EMI matrix as SciPy CSR (columns sorted); ``eliminated``: Dirichlet rows and columns replaced by the identity, the

@@ -5053,6 +5053,29 @@ int knp_get_stats(const knp_ctx* ctx, double* out) {
     out[KNP_ST_SPMV_DOTS] = (double)ctx->n_spmv_dots;
     return KNP_OK;
 }
+int knp_get_launch_info(const knp_ctx* ctx, int32_t* out, int n) {
+    if (!ctx || !out || n <= 0) return KNP_E_ARG;
+    const KnpHostGraph& g = ctx->g;
+    int32_t v[KNP_LI_COUNT];
+    v[KNP_LI_ASM_VARIANT] = ctx->asm_stage > 0 ? (ctx->d_tc_meta ? 2 : 1) : 0;
+    v[KNP_LI_ASM_STAGE] = ctx->asm_stage;
+    v[KNP_LI_ASM_DMAX] = ctx->asm_dmax;
+    v[KNP_LI_ASM_GROUP] = ctx->asm_group;
+    v[KNP_LI_SPMV_GROUP] = ctx->spmv_group;
+    v[KNP_LI_PC_GROUP] = ctx->pc_group;
+    v[KNP_LI_MAX_NODE_CELLS] = g.max_node_cells;
+    int dmax = 0;
+    if ((int)g.pair_ptr.size() > g.n_nodes_owned)
+        for (int node = 0; node < g.n_nodes_owned; ++node) dmax = std::max(dmax, g.pair_ptr[node + 1] - g.pair_ptr[node]);
+    v[KNP_LI_MAX_NODE_PAIRS] = dmax;
+    // the two switches the SpMV launch reads once per process, restated (launch_spmv_node)
+    static const int unroll = getenv("KNP_SPMV_UNROLL") ? atoi(getenv("KNP_SPMV_UNROLL")) : 2;
+    static const bool mf_off = getenv("KNP_SPMV_MF") && atoi(getenv("KNP_SPMV_MF")) == 0;
+    v[KNP_LI_SPMV_UNROLL] = unroll >= 2 ? 2 : 1;
+    v[KNP_LI_SPMV_MK] = (!mf_off && ctx->n_bc == 0 && ctx->d_pair_MK != nullptr) ? 1 : 0;
+    for (int i = 0; i < n && i < KNP_LI_COUNT; ++i) out[i] = v[i];
+    return KNP_OK;
+}
 
 }  // extern "C"
 

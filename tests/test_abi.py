@@ -31,6 +31,7 @@ def test_null_ctx_is_an_error_not_a_crash():
     from cgx_hip import _lib
     lib = _lib.load()
     assert lib.knp_set_nullspace(None, 1) < 0
+    assert lib.knp_get_launch_info(None, None, 0) < 0
     assert lib.knp_destroy(None) == 0
     assert lib.knp_last_error(None) == b"null ctx"
 
@@ -57,7 +58,7 @@ def test_product_never_imports_the_oracle():
 
 def test_host_graph_builder_under_address_sanitizer():
     """tools/asan/run.sh: the host-side graph builder (csrc/knp_setup.cpp) compiled with -fsanitize=address,undefined and run on a
-    small 2D and a small 3D mesh (GPU sanitizers are not available on the pool: CPU build only).  Skipped without libasan."""
+    small 2D and a small 3D generated mesh and on two irregular meshes with a high-valence vertex (GPU sanitizers are not available on the pool: CPU build only).  Skipped without libasan."""
     import shutil
     import subprocess
     import pytest
@@ -69,7 +70,7 @@ def test_host_graph_builder_under_address_sanitizer():
     r = subprocess.run(["bash", os.path.join(ROOT, "tools", "asan", "run.sh")], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     assert "ERROR: AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
-    assert r.stdout.count("rc=0") == 2, r.stdout
+    assert r.stdout.count("rc=0") == 4, r.stdout
 
 
 def test_host_threads_follow_the_cpu_share_of_the_process():

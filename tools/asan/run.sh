@@ -1,16 +1,21 @@
 #!/bin/bash
-# AddressSanitizer / UBSan run of the host-side graph builder (csrc/knp_setup.cpp) on small 2D and 3D meshes.
+# AddressSanitizer / UBSan run of the host-side graph builder (csrc/knp_setup.cpp) on small 2D and 3D meshes: the generated square and
+# cube, and two irregular meshes with a high-valence vertex (tests/irregular_meshes.py: 301 pairs at one node in 2D, 116 cells in 3D).
 # CPU build only (GPU sanitizers are not available on the pool).  usage: bash tools/asan/run.sh
 set -e
 ROOT=$(cd "$(dirname "$0")/../.." && pwd)
 W=$(mktemp -d)
 cd "$W"
 python - <<PY
-import sys; sys.path[:0]=['$ROOT/knp-emi-cgx_amd']
+import sys; sys.path[:0]=['$ROOT/knp-emi-cgx_amd','$ROOT/tests']
 import numpy as np
 from cgx_hip import mesh as M
-for name,(gen,N) in {"sq":(M.create_unit_square,12),"cu":(M.create_unit_cube,6)}.items():
-    coords,cells=gen(N); tags=M.mark_subdomains_box(coords,cells)
+import irregular_meshes as IM
+def generated(gen,N):
+    coords,cells=gen(N); return coords,cells,M.mark_subdomains_box(coords,cells)
+for name,mk in {"sq":lambda:generated(M.create_unit_square,12),"cu":lambda:generated(M.create_unit_cube,6),
+                "hub2d":lambda:IM.mesh("hub2d_12_300"),"hub3d":lambda:IM.mesh("hub3d_5_60")}.items():
+    coords,cells,tags=mk()
     gamma,gt,fv=M.gamma_integration_entities(cells,tags,(1,),(2,))
     side=np.where(tags==1,0,1).astype(np.uint8)
     qp,qw=M.facet_quadrature(coords.shape[1],10)
@@ -21,4 +26,4 @@ for name,(gen,N) in {"sq":(M.create_unit_square,12),"cu":(M.create_unit_cube,6)}
 PY
 g++ -std=c++17 -O1 -g -fsanitize=address,undefined -fno-omit-frame-pointer -fopenmp -D__HIP_PLATFORM_AMD__ -I/opt/rocm/include \
     -I"$ROOT/include" -I"$ROOT/knp-emi-cgx_amd/csrc" "$ROOT/tools/asan/graph_driver.cpp" "$ROOT/knp-emi-cgx_amd/csrc/knp_setup.cpp" -o drv
-ASAN_OPTIONS=detect_leaks=0 OMP_NUM_THREADS=4 ./drv sq.bin cu.bin
+ASAN_OPTIONS=detect_leaks=0 OMP_NUM_THREADS=4 ./drv sq.bin cu.bin hub2d.bin hub3d.bin
