@@ -323,7 +323,10 @@ int knp_gmres_prepare(knp_ctx* ctx, const double* b);
  * slots; anything larger is KNP_E_ARG).  b and x are [n_dof_local] device vectors.  On distributed contexts the GHOST entries
  * [n_dof_owned, n_dof_local) of b -- and of r in knp_pc_apply, b in knp_gmres_prepare -- are OVERWRITTEN by the halo exchange of
  * the preconditioner's fused level-0 leg although the arguments are const-qualified (the owned entries are never written);
- * on one GPU n_dof_local == n_dof_owned and nothing is written. */
+ * on one GPU n_dof_local == n_dof_owned and nothing is written.
+ * On one GPU without hooks, Dirichlet rows or deflation the first iteration of every cycle is enqueued before the host reads the
+ * cycle's initial residual norm (one wait per cycle start less; same kernels, order and results; KNP_GMRES_AHEAD=0, read at
+ * knp_pc_setup, restores the in-order form).  KNP_ST_READBACK and KNP_ST_ALLREDUCE count what ran, a discarded iteration included. */
 int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, double atol, int32_t max_it,
                     int32_t restart, int32_t* its, double* rnorm, int32_t* reason);
 /* Flexible GMRES(restart): what the reference gets from PETSc with ksp_type fgmres, or gmres with norm_type unpreconditioned

@@ -315,6 +315,7 @@ struct knp_ctx {
     int pc_kind = KNP_PC_NONE;
     int fused_dots = 1;       // first reduction stage in the cycle's last leg (KNP_FUSED_DOTS=0: off)
     int spmv_dots = 1;        // flexible GMRES: first reduction stage in the SpMV on A (KNP_SPMV_DOTS=0: off)
+    int gmres_ahead = 1;      // GMRES: iteration 0 of a cycle is enqueued before the residual norm is read (KNP_GMRES_AHEAD=0: off)
     double* d_vbj = nullptr;  // [n_nodes_owned*16] compact vertex blocks
     KnpAmgHier hier[KNP_MAX_HIER];   // 0: all fields (block-Jacobi form) or ion fields; 1: potential
     int amg_fp32 = 0;                // store the preconditioner's operators in fp32 (vectors and A stay fp64)

@@ -4652,6 +4652,7 @@ int knp_pc_setup(knp_ctx* ctx, int32_t kind) {
     ctx->pc_kind = kind;
     ctx->fused_dots = !(getenv("KNP_FUSED_DOTS") && atoi(getenv("KNP_FUSED_DOTS")) == 0);   // read at every knp_pc_setup, like KNP_FUSED
     ctx->spmv_dots = !(getenv("KNP_SPMV_DOTS") && atoi(getenv("KNP_SPMV_DOTS")) == 0);
+    ctx->gmres_ahead = !(getenv("KNP_GMRES_AHEAD") && atoi(getenv("KNP_GMRES_AHEAD")) == 0);
     for (int h = 0; h < KNP_MAX_HIER; ++h) ctx->hier[h].fused = 0;
     if (kind == KNP_PC_AMG) ctx->hier[0].fused = fused_eligible(ctx, ctx->hier[0]) ? 1 : 0;
     if (kind == KNP_PC_AMG_BT || kind == KNP_PC_AMG_LT) {   // both or none: the potential hierarchy then works on compact vectors

@@ -306,42 +306,51 @@ static int gm_read_state(const KrylovSolve& K, double* res, int* flag) {
 // follows by Pythagoras (explicit norm only when that would cancel, see k_givens).  The first stage of the reduction (partial sums per
 // block in d_partial) is either already there -- first_nb > 0 blocks at row stride first_stride, written by the kernel that produced
 // w: the preconditioner's last leg (RED_WIDE) or the SpMV (SPMV_WIDE) -- or runs here in k_multi_dot.
-static int arnoldi_step_finish(const KrylovSolve& K, int j, const double* w, double* vn, int first_nb, int first_stride, double* res, int* flag) {
+// Two halves: arnoldi_step_enqueue launches the reduction, the Givens step and v_{j+1} and waits for nothing;
+// arnoldi_step_read waits for the residual estimate and flag (`have`: the caller has read them already, they are in *res, *flag)
+// and runs the cancellation fallback.  arnoldi_step_finish is both, back to back.
+static int arnoldi_step_enqueue(const KrylovSolve& K, int j, const double* w, double* vn, int first_nb, int first_stride) {
     knp_ctx* ctx = K.ctx;
     hipStream_t st = ctx->stream;
     const GmLayout GL = K.GL;
     double* gm = K.gm;
     const int n = K.n, nb = K.nb, nsi = K.ns ? 1 : 0;
     const int64_t ldv = K.ldv;
-    {
-        ProfScope ps(ctx, 1);
-        const bool done = first_nb > 0;
-        const int nbr = done ? first_nb : nb;   // partial blocks of the first stage, and their row stride
-        const int pst = done ? first_stride : RED_BLOCKS;
-        for (int i0 = 0; i0 <= j && !done; i0 += 8) {   // owned rows; the first launch also takes the gauge coefficient and w.w
-            if (i0 == 0 && K.ns)
-                hipLaunchKernelGGL((k_multi_dot<8, true, true>), dim3(nb), dim3(NT), 0, st, n, ldv, i0, j + 1, ctx->d_V, w, ctx->d_partial);
-            else if (i0 == 0)
-                hipLaunchKernelGGL((k_multi_dot<8, false, true>), dim3(nb), dim3(NT), 0, st, n, ldv, i0, j + 1, ctx->d_V, w, ctx->d_partial);
-            else
-                hipLaunchKernelGGL((k_multi_dot<8, false, false>), dim3(nb), dim3(NT), 0, st, n, ldv, i0, j + 1, ctx->d_V, w, ctx->d_partial);
-        }
-        const int nred = j + 2 + nsi;
-        if (fin_ok(ctx)) {   // one GPU: second reduction stage + Givens step in one single-block kernel
-            ++ctx->n_allreduce;
-            hipLaunchKernelGGL(k_reduce_fin, dim3(1), dim3(NT), 0, st, 1, nbr, nred, ctx->d_partial, ctx->d_red, 0, GL, j, nsi, K.inv_cnt, gm,
-                               0, 0.0, ctx->mirror() ? ctx->h_red_dev + GM_RES : nullptr, ctx->mirror() ? ctx->h_seq_dev : nullptr, ++ctx->seq_counter,
-                               pst);
-        } else {   // (a first stage done elsewhere implies fin_ok -- k_reduce_partials takes no stride -- so nbr = nb here)
-            hipLaunchKernelGGL(k_reduce_partials, dim3(nred), dim3(NT), 0, st, nbr, ctx->d_partial, ctx->d_red, 0, (double*)nullptr);
-            KCHK(allreduce_slots(ctx, 0, nred));
-            hipLaunchKernelGGL(k_givens, dim3(1), dim3(64), 0, st, GL, j, nsi, K.inv_cnt, ctx->d_red, -1, gm,
-                               ctx->mirror() ? ctx->h_red_dev + GM_RES : nullptr, ctx->mirror() ? ctx->h_seq_dev : nullptr, ++ctx->seq_counter);
-        }
-        hipLaunchKernelGGL(k_update_scale, dim3(nb), dim3(NT), 0, st, n, ldv, j + 1, ctx->d_V, ctx->d_red, w, gm + GL.st(), K.inv_cnt, vn);
-        HIPCHK(hipGetLastError());
+    ProfScope ps(ctx, 1);
+    const bool done = first_nb > 0;
+    const int nbr = done ? first_nb : nb;   // partial blocks of the first stage, and their row stride
+    const int pst = done ? first_stride : RED_BLOCKS;
+    for (int i0 = 0; i0 <= j && !done; i0 += 8) {   // owned rows; the first launch also takes the gauge coefficient and w.w
+        if (i0 == 0 && K.ns)
+            hipLaunchKernelGGL((k_multi_dot<8, true, true>), dim3(nb), dim3(NT), 0, st, n, ldv, i0, j + 1, ctx->d_V, w, ctx->d_partial);
+        else if (i0 == 0)
+            hipLaunchKernelGGL((k_multi_dot<8, false, true>), dim3(nb), dim3(NT), 0, st, n, ldv, i0, j + 1, ctx->d_V, w, ctx->d_partial);
+        else
+            hipLaunchKernelGGL((k_multi_dot<8, false, false>), dim3(nb), dim3(NT), 0, st, n, ldv, i0, j + 1, ctx->d_V, w, ctx->d_partial);
     }
-    KCHK(gm_read_state(K, res, flag));
+    const int nred = j + 2 + nsi;
+    if (fin_ok(ctx)) {   // one GPU: second reduction stage + Givens step in one single-block kernel
+        ++ctx->n_allreduce;
+        hipLaunchKernelGGL(k_reduce_fin, dim3(1), dim3(NT), 0, st, 1, nbr, nred, ctx->d_partial, ctx->d_red, 0, GL, j, nsi, K.inv_cnt, gm,
+                           0, 0.0, ctx->mirror() ? ctx->h_red_dev + GM_RES : nullptr, ctx->mirror() ? ctx->h_seq_dev : nullptr, ++ctx->seq_counter,
+                           pst);
+    } else {   // (a first stage done elsewhere implies fin_ok -- k_reduce_partials takes no stride -- so nbr = nb here)
+        hipLaunchKernelGGL(k_reduce_partials, dim3(nred), dim3(NT), 0, st, nbr, ctx->d_partial, ctx->d_red, 0, (double*)nullptr);
+        KCHK(allreduce_slots(ctx, 0, nred));
+        hipLaunchKernelGGL(k_givens, dim3(1), dim3(64), 0, st, GL, j, nsi, K.inv_cnt, ctx->d_red, -1, gm,
+                           ctx->mirror() ? ctx->h_red_dev + GM_RES : nullptr, ctx->mirror() ? ctx->h_seq_dev : nullptr, ++ctx->seq_counter);
+    }
+    hipLaunchKernelGGL(k_update_scale, dim3(nb), dim3(NT), 0, st, n, ldv, j + 1, ctx->d_V, ctx->d_red, w, gm + GL.st(), K.inv_cnt, vn);
+    HIPCHK(hipGetLastError());
+    return KNP_OK;
+}
+static int arnoldi_step_read(const KrylovSolve& K, int j, double* vn, double* res, int* flag, bool have = false) {
+    knp_ctx* ctx = K.ctx;
+    hipStream_t st = ctx->stream;
+    const GmLayout GL = K.GL;
+    double* gm = K.gm;
+    const int n = K.n, nb = K.nb, nsi = K.ns ? 1 : 0;
+    if (!have) KCHK(gm_read_state(K, res, flag));
     if (*flag == 1) {   // cancellation: explicit norm of the (unnormalised) vector, second reduction of this iteration
         ProfScope ps(ctx, 1);
         ++ctx->n_norm_fallback;
@@ -355,6 +364,10 @@ static int arnoldi_step_finish(const KrylovSolve& K, int j, const double* w, dou
         KCHK(gm_read_state(K, res, flag));
     }
     return KNP_OK;
+}
+static int arnoldi_step_finish(const KrylovSolve& K, int j, const double* w, double* vn, int first_nb, int first_stride, double* res, int* flag) {
+    KCHK(arnoldi_step_enqueue(K, j, w, vn, first_nb, first_stride));
+    return arnoldi_step_read(K, j, vn, res, flag);
 }
 
 // after iteration j: counts it, sets *jd to the number of columns the update of x may use; true = the solve ends here (*reason set)
@@ -441,6 +454,36 @@ int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doubl
     const bool ns = ctx->ns_on && cnt > 0;
     K.ns = ns;
     K.inv_cnt = ns ? 1.0 / (double)cnt : 0.0;
+    // one cycle start in its launch pieces: v_0 = B r / beta with g = (beta, 0, ...), and iteration j up to v_{j+1} (no host wait in either)
+    auto enqueue_v0 = [&](bool fused_norm) {
+        if (fused_norm) {
+            hipLaunchKernelGGL(k_scale_rsqrt_proj, dim3(K.vec_blocks), dim3(NT), 0, st, n, ctx->d_w, ctx->d_red + 60, ctx->d_red + 62,
+                               1.0 / (double)cnt, ctx->d_V, gm + GL.g(), m);
+        } else {
+            hipLaunchKernelGGL(k_scale_rsqrt, dim3(K.vec_blocks), dim3(NT), 0, st, n, ctx->d_w, ctx->d_red + 60, ctx->d_V);
+            hipLaunchKernelGGL(k_gm_init, dim3(1), dim3(64), 0, st, GL, gm, ctx->d_red + 60);
+        }
+    };
+    auto enqueue_iteration = [&](int j) -> int {
+        double* vj = ctx->d_V + (size_t)j * ldv;
+        double* vn = ctx->d_V + (size_t)(j + 1) * ldv;
+        KCHK(spmv_A(ctx, vj, nullptr, ctx->d_t, false));
+        // The null-space removal that follows the preconditioner (KSP_RemoveNullSpace) is folded into the
+        // Gram-Schmidt pass: the basis vectors are orthogonal to ns, so h_i = V_i.(w - ns ns.w) = V_i.w, and the
+        // projection itself is one more "basis vector" in the update (same reduction, no extra all-reduce).
+        // The first stage of that reduction runs in the preconditioner's last leg where that can take it (DotReq), else in
+        // k_multi_dot (arnoldi_step_enqueue).
+        DotReq dq{j + 1, ns, ldv, ctx->d_V, ctx->d_partial};
+        KCHK(pc_apply_proj(ctx, ctx->d_t, ctx->d_w, ns ? 0 : cnt, (ctx->fused_dots && fin_ok(ctx) && j + 1 <= BU_MAX_M) ? &dq : nullptr));
+        return arnoldi_step_enqueue(K, j, ctx->d_w, vn, dq.done ? dq.nb : 0, RED_WIDE);
+    };
+    // Enqueue-ahead form of a cycle start: nothing on the device depends on the host's reading of ||B r||, so v_0 and iteration 0 are
+    // launched behind the norm's reduction and the host waits ONCE, for iteration 0's k_reduce_fin (stream order: the norm's has
+    // finished by then).  The decisions are taken afterwards, the same ones in the same order; an entry that ends or repairs the
+    // cycle start discards iteration 0, which has written V_0, V_1, gm, d_t, d_w and reduction slots but not x.  One GPU, no hooks:
+    // there every reduction publishes to the pinned mirror and the sequence word, through k_reduce_fin or (KNP_FIN=0) k_proj_norm / k_givens.
+    const bool ahead_ok = ctx->gmres_ahead && ctx->mirror() && ctx->h_seq && ctx->h_seq_dev && !ctx->halo && !ctx->allreduce && !ctx->p2p &&
+                          !ctx->level_comm && ctx->defl_m == 0 && ctx->n_bc == 0 && max_it > 0 && (ctx->prof_on & ~1) == 0;
     while (true) {
         // r = M (b - A x)
         KCHK(spmv_A(ctx, x, b, ctx->d_t, true));
@@ -458,7 +501,24 @@ int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doubl
             KCHK(rcs);
             HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
         }
-        KCHK(pc_norm_read(ctx, ctx->d_w, cnt, &fused_norm));
+        bool ahead = ahead_ok && fused_norm;   // true while iteration 0 of this cycle is in flight (or done) and still valid
+        double res_a = 0.0;
+        int flag_a = 0;
+        // the residual chain again, in order, after iteration 0 (or the ||B b|| repair) overwrote d_t and d_w (rare)
+        auto redo_residual = [&]() -> int {
+            if (ahead) KCHK(spmv_A(ctx, x, b, ctx->d_t, true));
+            ahead = false;
+            KCHK(pc_apply_norm(ctx, ctx->d_t, ctx->d_w, cnt, &fused_norm));
+            return pc_norm_read(ctx, ctx->d_w, cnt, &fused_norm);
+        };
+        if (ahead) {
+            enqueue_v0(true);
+            KCHK(enqueue_iteration(0));
+            KCHK(gm_read_state(K, &res_a, &flag_a));   // the one wait; slots 60, 61 of the mirror are the norm's
+            if (ctx->h_red[61] != 0.0) KCHK(redo_residual());   // cancellation in the residual norm: pc_norm_read projects explicitly
+        } else {
+            KCHK(pc_norm_read(ctx, ctx->d_w, cnt, &fused_norm));
+        }
         if (lazy_bnorm) {   // join the side stream now: its cycle ran next to the SpMV and the cycle above
             lazy_bnorm = false;
             HIPCHK(hipEventSynchronize(ctx->ev_join));
@@ -471,8 +531,7 @@ int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doubl
                 KCHK(read_slots(ctx, 60, 1, ctx->seq_counter));
                 nb2 = ctx->h_red[60];
                 // ... which used the slots and vectors of the residual norm above: redo that one (rare)
-                KCHK(pc_apply_norm(ctx, ctx->d_t, ctx->d_w, cnt, &fused_norm));
-                KCHK(pc_norm_read(ctx, ctx->d_w, cnt, &fused_norm));
+                KCHK(redo_residual());
             }
             bnorm = std::sqrt(nb2);
             ctx->last_bnorm = bnorm;
@@ -485,28 +544,15 @@ int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doubl
         if (!std::isfinite(beta)) { *reason = KNP_DIVERGED_NANORINF; break; }
         if (beta <= K.ttol) { *reason = (beta <= atol) ? KNP_CONVERGED_ATOL : KNP_CONVERGED_RTOL; break; }
         if (it >= max_it) { *reason = KNP_DIVERGED_ITS; break; }
-        if (fused_norm) {
-            hipLaunchKernelGGL(k_scale_rsqrt_proj, dim3(K.vec_blocks), dim3(NT), 0, st, n, ctx->d_w, ctx->d_red + 60, ctx->d_red + 62,
-                               1.0 / (double)cnt, ctx->d_V, gm + GL.g(), m);
-        } else {
-            hipLaunchKernelGGL(k_scale_rsqrt, dim3(K.vec_blocks), dim3(NT), 0, st, n, ctx->d_w, ctx->d_red + 60, ctx->d_V);
-            hipLaunchKernelGGL(k_gm_init, dim3(1), dim3(64), 0, st, GL, gm, ctx->d_red + 60);
-        }
+        if (!ahead) enqueue_v0(fused_norm);
         int jd = 0;
         bool stop = false;
         for (int j = 0; j < m; ++j) {
-            double* vj = ctx->d_V + (size_t)j * ldv;
-            double* vn = ctx->d_V + (size_t)(j + 1) * ldv;
-            KCHK(spmv_A(ctx, vj, nullptr, ctx->d_t, false));
-            // The null-space removal that follows the preconditioner (KSP_RemoveNullSpace) is folded into the
-            // Gram-Schmidt pass: the basis vectors are orthogonal to ns, so h_i = V_i.(w - ns ns.w) = V_i.w, and the
-            // projection itself is one more "basis vector" in the update (same reduction, no extra all-reduce).
-            // The first stage of that reduction runs in the preconditioner's last leg where that can take it (DotReq), else in
-            // k_multi_dot (arnoldi_step_finish).
-            DotReq dq{j + 1, ns, ldv, ctx->d_V, ctx->d_partial};
-            KCHK(pc_apply_proj(ctx, ctx->d_t, ctx->d_w, ns ? 0 : cnt, (ctx->fused_dots && fin_ok(ctx) && j + 1 <= BU_MAX_M) ? &dq : nullptr));
-            int flag = 0;
-            KCHK(arnoldi_step_finish(K, j, ctx->d_w, vn, dq.done ? dq.nb : 0, RED_WIDE, &res, &flag));
+            const bool have = ahead && j == 0;   // iteration 0 ran ahead: its residual estimate and flag were read at the wait above
+            int flag = have ? flag_a : 0;
+            if (have) res = res_a;
+            else KCHK(enqueue_iteration(j));
+            KCHK(arnoldi_step_read(K, j, ctx->d_V + (size_t)(j + 1) * ldv, &res, &flag, have));
             if (krylov_stop_test(K, j, flag, res, max_it, &it, &jd, reason)) { stop = true; break; }
         }
         if (jd > 0) {
