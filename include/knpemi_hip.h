@@ -497,6 +497,21 @@ enum { KNP_LI_ASM_VARIANT = 0 /* volume assembly: 0 plain gather, 1 staged with 
        KNP_LI_SPMV_MK = 9 /* 1: the SpMV on A reads {M, K} per pair, 0: the stored time-invariant entries (Dirichlet rows, KNP_SPMV_MF=0) */,
        KNP_LI_COUNT = 10 };
 int knp_get_launch_info(const knp_ctx* ctx, int32_t* out /* host [n] */, int n);
+/* what one level of an uploaded hierarchy runs on, and the cycle form knp_pc_setup chose for the hierarchy (context fields only;
+ * nothing is launched): the first min(n, KNP_AI_COUNT) slots are written.  Lanes per row of the generic CSR kernels for the operators
+ * the level carries, lanes per node row of their node-blocked copies (0: no such copy).  KNP_E_ARG for a null argument, n <= 0, or a
+ * hierarchy / level that does not exist.  cgx_hip/backend.py (Backend.AMG_LEVEL_INFO) names the slots in this order: a slot added here is
+ * added there (tests/test_synthetic_hierarchies_host.py compares the two). */
+enum { KNP_AI_A_LANES = 0, KNP_AI_P_LANES = 1, KNP_AI_R_LANES = 2, KNP_AI_S_LANES = 3, KNP_AI_RT_LANES = 4, KNP_AI_U_LANES = 5,
+       KNP_AI_BA_LANES = 6, KNP_AI_BR_LANES = 7, KNP_AI_BS_LANES = 8, KNP_AI_BRT_LANES = 9, KNP_AI_BU_LANES = 10,
+       KNP_AI_P_N_ACT = 11, KNP_AI_S_N_ACT = 12 /* > 0: the kernel walks a compact list of this many non-empty rows */,
+       KNP_AI_LFUSED = 13 /* the level runs in fused form inside the level-by-level cycle */,
+       KNP_AI_N = 14, KNP_AI_N_COARSE = 15, KNP_AI_FP32 = 16 /* operator values are stored in fp32 */,
+       KNP_AI_H_FUSED = 17, KNP_AI_H_BLOCKED = 18, KNP_AI_H_CFUSED = 19, KNP_AI_H_L0_FUSED = 20 /* of the hierarchy, as of the last knp_pc_setup */,
+       KNP_AI_H_NC = 21 /* size of the dense coarse inverse (0: the last level smooths) */,
+       KNP_AI_H_CINV_F32 = 22 /* the dense coarse inverse is applied from an fp32 copy */,
+       KNP_AI_COUNT = 23 };
+int knp_amg_get_level_info(const knp_ctx* ctx, int32_t hier, int32_t level, int32_t* out /* host [n] */, int n);
 
 #ifdef __cplusplus
 }

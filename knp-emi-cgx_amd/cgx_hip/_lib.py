@@ -146,6 +146,7 @@ SIGNATURES = {
     "knp_get_stats": (C.c_int, [vp, f64p]),
     "knp_get_traffic_model": (C.c_int, [vp, f64p]),
     "knp_get_launch_info": (C.c_int, [vp, i32p, C.c_int]),
+    "knp_amg_get_level_info": (C.c_int, [vp, C.c_int32, C.c_int32, i32p, C.c_int]),
 }
 
 _lib = None

@@ -736,6 +736,16 @@ class Backend:
         self.check(self.lib.knp_get_launch_info(self.ctx, out, len(names)))
         return dict(zip(names, (int(v) for v in out)))
 
+    AMG_LEVEL_INFO = ["A_lanes", "P_lanes", "R_lanes", "S_lanes", "Rt_lanes", "U_lanes", "bA_lanes", "bR_lanes", "bS_lanes", "bRt_lanes",
+                      "bU_lanes", "P_n_act", "S_n_act", "lfused", "n", "n_coarse", "fp32", "fused", "blocked", "cfused", "l0_fused", "nc", "cinv_f32"]
+
+    def amg_level_info(self, hier, level):
+        """what level ``level`` of hierarchy ``hier`` runs on and the cycle form the last ``pc_setup`` chose (knp_amg_get_level_info;
+        nothing is launched): lanes per row of the generic and of the node-blocked kernels (0: operator absent), sizes, storage"""
+        out = (C.c_int32 * len(self.AMG_LEVEL_INFO))()      # KNP_AI_COUNT
+        self.check(self.lib.knp_amg_get_level_info(self.ctx, hier, level, out, len(self.AMG_LEVEL_INFO)))
+        return dict(zip(self.AMG_LEVEL_INFO, (int(v) for v in out)))
+
     def profile_get(self):
         names = ["spmv", "orthogonalisation", "pc", "assembly", "other"]
         out = {}

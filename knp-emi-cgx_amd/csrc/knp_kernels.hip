@@ -5077,6 +5077,39 @@ int knp_get_launch_info(const knp_ctx* ctx, int32_t* out, int n) {
     for (int i = 0; i < n && i < KNP_LI_COUNT; ++i) out[i] = v[i];
     return KNP_OK;
 }
+int knp_amg_get_level_info(const knp_ctx* ctx, int32_t hier, int32_t level, int32_t* out, int n) {
+    if (!ctx || !out || n <= 0 || hier < 0 || hier >= KNP_MAX_HIER) return KNP_E_ARG;
+    const KnpAmgHier& H = ctx->hier[hier];
+    if (level < 0 || level >= H.levels) return KNP_E_ARG;
+    const KnpAmgLevel& L = H.lv[level];
+    auto blanes = [](const KnpBlockedCsr& b) { return b.rp ? b.lanes : 0; };
+    int32_t v[KNP_AI_COUNT];
+    v[KNP_AI_A_LANES] = L.A_lanes;
+    v[KNP_AI_P_LANES] = L.P_rp ? L.P_lanes : 0;
+    v[KNP_AI_R_LANES] = L.R_rp ? L.R_lanes : 0;
+    v[KNP_AI_S_LANES] = L.S_rp ? L.S_lanes : 0;
+    v[KNP_AI_RT_LANES] = L.Rt_rp ? L.Rt_lanes : 0;
+    v[KNP_AI_U_LANES] = L.U_rp ? L.U_lanes : 0;
+    v[KNP_AI_BA_LANES] = blanes(L.bA);
+    v[KNP_AI_BR_LANES] = blanes(L.bR);
+    v[KNP_AI_BS_LANES] = blanes(L.bS);
+    v[KNP_AI_BRT_LANES] = blanes(L.bRt);
+    v[KNP_AI_BU_LANES] = blanes(L.bU);
+    v[KNP_AI_P_N_ACT] = L.P_n_act;
+    v[KNP_AI_S_N_ACT] = L.S_n_act;
+    v[KNP_AI_LFUSED] = L.lfused;
+    v[KNP_AI_N] = L.n;
+    v[KNP_AI_N_COARSE] = L.n_coarse;
+    v[KNP_AI_FP32] = (L.A_vf || L.R_vf || L.S_vf) ? 1 : 0;
+    v[KNP_AI_H_FUSED] = H.fused;
+    v[KNP_AI_H_BLOCKED] = H.blocked;
+    v[KNP_AI_H_CFUSED] = H.cfused;
+    v[KNP_AI_H_L0_FUSED] = H.l0_fused;
+    v[KNP_AI_H_NC] = H.nc;
+    v[KNP_AI_H_CINV_F32] = H.cinv_f != nullptr ? 1 : 0;
+    for (int i = 0; i < n && i < KNP_AI_COUNT; ++i) out[i] = v[i];
+    return KNP_OK;
+}
 
 }  // extern "C"
 

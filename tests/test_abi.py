@@ -32,6 +32,7 @@ def test_null_ctx_is_an_error_not_a_crash():
     lib = _lib.load()
     assert lib.knp_set_nullspace(None, 1) < 0
     assert lib.knp_get_launch_info(None, None, 0) < 0
+    assert lib.knp_amg_get_level_info(None, 0, 0, None, 0) < 0
     assert lib.knp_destroy(None) == 0
     assert lib.knp_last_error(None) == b"null ctx"
 
