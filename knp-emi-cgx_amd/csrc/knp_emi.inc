@@ -393,12 +393,10 @@ static void emi_launch_spmv(knp_ctx* ctx, const double* x, const double* b, doub
     const int n = ctx->g.n_nodes_owned;
     constexpr int G = 8;
     const int nb = std::min(EMI_SPMV_BLOCKS, nblocks((int64_t)n * G));
-#define KNP_EMI_SPMV(BCC)                                                                                                              \
-    hipLaunchKernelGGL((k_emi_spmv<G, MODE, BCC, DOT>), dim3(nb), dim3(NT), 0, ctx->stream, n, ctx->d_pair_ptr, ctx->d_pair_col, E.d_val, \
-                       ctx->d_node_gv, ctx->d_node_side, ctx->d_gptr, ctx->d_gx_i, ctx->d_gx_e, E.d_xval, E.d_mask, x, b, y, ctx->d_partial)
-    if (E.n_bc > 0) KNP_EMI_SPMV(true);
-    else KNP_EMI_SPMV(false);
-#undef KNP_EMI_SPMV
+    with_flag(E.n_bc > 0, [&](auto BC) {
+        hipLaunchKernelGGL((k_emi_spmv<G, MODE, BC(), DOT>), dim3(nb), dim3(NT), 0, ctx->stream, n, ctx->d_pair_ptr, ctx->d_pair_col, E.d_val,
+                           ctx->d_node_gv, ctx->d_node_side, ctx->d_gptr, ctx->d_gx_i, ctx->d_gx_e, E.d_xval, E.d_mask, x, b, y, ctx->d_partial);
+    });
 }
 static inline int emi_spmv_blocks(const knp_ctx* ctx) { return std::min(EMI_SPMV_BLOCKS, nblocks((int64_t)ctx->g.n_nodes_owned * 8)); }
 
@@ -577,13 +575,11 @@ int knp_emi_assemble_rhs(knp_ctx* ctx, const knp_fields* fields, const double* f
         const size_t lds = (size_t)std::max(ctx->prog_regs, 1) * EMI_BT * sizeof(double);
         if (lds > 64 * 1024) { ctx->err = "membrane programs need more LDS than the EMI facet kernel has"; return KNP_E_STATE; }
         const int n_progs = ctx->max_prog + 1;
-#define KNP_EMI_FACETS(D)                                                                                                                     \
-    hipLaunchKernelGGL(k_emi_facets<D>, dim3(nblocks(g.n_g, EMI_BT)), dim3(EMI_BT), lds, ctx->stream, g.n_g, g.n_q, E.C_M, E.dt, ctx->d_fv,      \
-                       ctx->d_fmeas, ctx->d_qp, ctx->d_qw, fields->phi_m, aux, n_aux, ctx->d_coords, ctx->d_gamma_prog, n_progs,                 \
-                       (const int32_t* const*)ctx->d_prog_code, (const int32_t*)ctx->d_prog_len, (const double* const*)ctx->d_prog_consts, E.d_fvec)
-        if (g.dim == 2) KNP_EMI_FACETS(2);
-        else KNP_EMI_FACETS(3);
-#undef KNP_EMI_FACETS
+        with_either<2, 3>(g.dim == 2, [&](auto D) {
+            hipLaunchKernelGGL(k_emi_facets<D()>, dim3(nblocks(g.n_g, EMI_BT)), dim3(EMI_BT), lds, ctx->stream, g.n_g, g.n_q, E.C_M, E.dt, ctx->d_fv,
+                               ctx->d_fmeas, ctx->d_qp, ctx->d_qw, fields->phi_m, aux, n_aux, ctx->d_coords, ctx->d_gamma_prog, n_progs,
+                               (const int32_t* const*)ctx->d_prog_code, (const int32_t*)ctx->d_prog_len, (const double* const*)ctx->d_prog_consts, E.d_fvec);
+        });
     }
     if (n > 0) {
         constexpr int G = 8;

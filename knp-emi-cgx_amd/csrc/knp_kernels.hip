@@ -25,6 +25,7 @@
 #include <cstring>
 #include <new>
 
+#include "knp_dispatch.hpp"
 #include "knp_internal.hpp"
 
 #define HIPCHK(call)                                                                       \
@@ -464,49 +465,30 @@ static void launch_assemble_nodes(knp_ctx* ctx, const DevParams& P, double* at, 
     if (ctx->asm_stage > 0 && ctx->d_tc_meta) {   // staged + transposed contribution lists (default)
         const int cmax = ctx->asm_stage;
         const int dmax = ctx->asm_dmax, nv1 = g.nv1;
-#define KNP_ASMT2(GG, FF) hipLaunchKernelGGL((k_assemble_nodes_tr<PRECOND, TD_ONLY, GG, FF>), dim3(nblocks((int64_t)n * GG)), dim3(NT),                  \
-                                        (size_t)(NT / GG) * (cmax + dmax) * 3 * sizeof(double), ctx->stream, n, P, cmax, ctx->d_pair_ptr, ctx->d_node_side, \
-                                        ctx->d_pair_M, ctx->d_pair_K, ctx->d_tc_meta, ctx->d_tc_slot, ctx->d_tc_k, ctx->d_node_cell_ptr,              \
-                                        ctx->d_node_cell, ctx->d_cbar, at, ac, ctx->d_pair_col, ctx->d_ncv, ctx->d_knod, dmax, nv1)
-#define KNP_ASMT(GG) do { if (dmax > 0) KNP_ASMT2(GG, true); else KNP_ASMT2(GG, false); } while (0)
-        switch (ctx->asm_group) {
-            case 4: KNP_ASMT(4); break;
-            case 8: KNP_ASMT(8); break;
-            case 16: KNP_ASMT(16); break;
-            default: KNP_ASMT(32); break;
-        }
-#undef KNP_ASMT
-#undef KNP_ASMT2
+        with_lanes<4, 32>(ctx->asm_group, [&](auto G) { with_flag(dmax > 0, [&](auto F) {
+            hipLaunchKernelGGL((k_assemble_nodes_tr<PRECOND, TD_ONLY, G(), F()>), dim3(nblocks((int64_t)n * G())), dim3(NT),
+                               (size_t)(NT / G()) * (cmax + dmax) * 3 * sizeof(double), ctx->stream, n, P, cmax, ctx->d_pair_ptr, ctx->d_node_side,
+                               ctx->d_pair_M, ctx->d_pair_K, ctx->d_tc_meta, ctx->d_tc_slot, ctx->d_tc_k, ctx->d_node_cell_ptr,
+                               ctx->d_node_cell, ctx->d_cbar, at, ac, ctx->d_pair_col, ctx->d_ncv, ctx->d_knod, dmax, nv1);
+        }); });
         return;
     }
     if (ctx->asm_stage > 0) {   // cell means staged in LDS (default)
         const int cmax = ctx->asm_stage;
         const int dmax = ctx->asm_dmax, nv1 = g.nv1;
-#define KNP_ASMS2(GG, FF) hipLaunchKernelGGL((k_assemble_nodes_staged<PRECOND, TD_ONLY, GG, FF>), dim3(nblocks((int64_t)n * GG)), dim3(NT),              \
-                                        (size_t)(NT / GG) * (cmax + dmax) * 3 * sizeof(double), ctx->stream, n, P, cmax, ctx->d_pair_ptr, ctx->d_pair_col,  \
-                                        ctx->d_node_side, ctx->d_pair_M, ctx->d_pair_K, ctx->d_contrib_ptr, ctx->d_contrib_slot, ctx->d_contrib_k, \
-                                        ctx->d_node_cell_ptr, ctx->d_node_cell, ctx->d_cbar, at, ac, ctx->d_ncv, ctx->d_knod, dmax, nv1)
-#define KNP_ASMS(GG) do { if (dmax > 0) KNP_ASMS2(GG, true); else KNP_ASMS2(GG, false); } while (0)
-        switch (ctx->asm_group) {
-            case 4: KNP_ASMS(4); break;
-            case 8: KNP_ASMS(8); break;
-            case 16: KNP_ASMS(16); break;
-            default: KNP_ASMS(32); break;
-        }
-#undef KNP_ASMS
-#undef KNP_ASMS2
+        with_lanes<4, 32>(ctx->asm_group, [&](auto G) { with_flag(dmax > 0, [&](auto F) {
+            hipLaunchKernelGGL((k_assemble_nodes_staged<PRECOND, TD_ONLY, G(), F()>), dim3(nblocks((int64_t)n * G())), dim3(NT),
+                               (size_t)(NT / G()) * (cmax + dmax) * 3 * sizeof(double), ctx->stream, n, P, cmax, ctx->d_pair_ptr, ctx->d_pair_col,
+                               ctx->d_node_side, ctx->d_pair_M, ctx->d_pair_K, ctx->d_contrib_ptr, ctx->d_contrib_slot, ctx->d_contrib_k,
+                               ctx->d_node_cell_ptr, ctx->d_node_cell, ctx->d_cbar, at, ac, ctx->d_ncv, ctx->d_knod, dmax, nv1);
+        }); });
         return;
     }
-#define KNP_ASM(GG) hipLaunchKernelGGL((k_assemble_nodes<PRECOND, TD_ONLY, GG>), dim3(nblocks((int64_t)n * GG)), dim3(NT), 0, ctx->stream, n, P, ctx->d_pair_ptr, \
-                                       ctx->d_pair_col, ctx->d_node_side, ctx->d_pair_M, ctx->d_pair_K, ctx->d_contrib_ptr, ctx->d_contrib_cell,       \
-                                       ctx->d_contrib_k, ctx->d_cbar, at, ac)
-    switch (ctx->asm_group) {
-        case 4: KNP_ASM(4); break;
-        case 8: KNP_ASM(8); break;
-        case 16: KNP_ASM(16); break;
-        default: KNP_ASM(32); break;
-    }
-#undef KNP_ASM
+    with_lanes<4, 32>(ctx->asm_group, [&](auto G) {
+        hipLaunchKernelGGL((k_assemble_nodes<PRECOND, TD_ONLY, G()>), dim3(nblocks((int64_t)n * G())), dim3(NT), 0, ctx->stream, n, P, ctx->d_pair_ptr,
+                           ctx->d_pair_col, ctx->d_node_side, ctx->d_pair_M, ctx->d_pair_K, ctx->d_contrib_ptr, ctx->d_contrib_cell,
+                           ctx->d_contrib_k, ctx->d_cbar, at, ac);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -776,21 +758,11 @@ static void launch_spmv_node(knp_ctx* ctx, int n_list, const int32_t* nodes, con
     const DevParams P = make_params(ctx);
     const AcCoef ci = ac_coef(P, 0), ce = ac_coef(P, 1);
     static const int unroll = getenv("KNP_SPMV_UNROLL") ? atoi(getenv("KNP_SPMV_UNROLL")) : 2;
-#define KNP_SPMV_NODE3(GG, MFF, UU)                                                                                                    \
-    hipExtLaunchKernelGGL((k_spmv_node<GG, MODE, MFF, UU>), dim3(nblocks((int64_t)n_list * GG)), dim3(NT), 0, ctx->stream, ev_a, ev_b, 0, n_list, nodes, \
-                          ctx->d_pair_ptr, ctx->d_pair_col, ctx->d_ac, ctx->d_pair_MK, ci, ce, ctx->d_at, ctx->d_node_gv, ctx->d_node_side, ctx->d_gptr, ctx->d_gx_i, \
-                          ctx->d_gx_e, ctx->d_ax, x, b, y)
-#define KNP_SPMV_NODE2(GG, MFF) do { if (unroll >= 2) KNP_SPMV_NODE3(GG, MFF, 2); else KNP_SPMV_NODE3(GG, MFF, 1); } while (0)
-#define KNP_SPMV_NODE(GG) do { if (mf) KNP_SPMV_NODE2(GG, true); else KNP_SPMV_NODE2(GG, false); } while (0)
-    switch (ctx->spmv_group) {
-        case 4: KNP_SPMV_NODE(4); break;
-        case 8: KNP_SPMV_NODE(8); break;
-        case 16: KNP_SPMV_NODE(16); break;
-        default: KNP_SPMV_NODE(32); break;
-    }
-#undef KNP_SPMV_NODE
-#undef KNP_SPMV_NODE2
-#undef KNP_SPMV_NODE3
+    with_lanes<4, 32>(ctx->spmv_group, [&](auto G) { with_flag(mf, [&](auto MF) { with_either<1, 2>(unroll < 2, [&](auto U) {
+        hipExtLaunchKernelGGL((k_spmv_node<G(), MODE, MF(), U()>), dim3(nblocks((int64_t)n_list * G())), dim3(NT), 0, ctx->stream, ev_a, ev_b, 0, n_list, nodes,
+                              ctx->d_pair_ptr, ctx->d_pair_col, ctx->d_ac, ctx->d_pair_MK, ci, ce, ctx->d_at, ctx->d_node_gv, ctx->d_node_side, ctx->d_gptr, ctx->d_gx_i,
+                              ctx->d_gx_e, ctx->d_ax, x, b, y);
+    }); }); });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -873,12 +845,9 @@ k_pnode(int n_nodes, int n_col_nodes, const int32_t* __restrict__ pair_ptr, cons
 template <int MODE, int FM, typename VT>
 static void launch_pnode_fm(hipStream_t st, int G, int n_nodes, int ncn, const int32_t* pp, const int32_t* pc, const VT* pv,
                             const double* dinv, const double* b, const double* xin, double c1, double c2, double* d, double* xout) {
-    switch (G) {
-        case 4: hipLaunchKernelGGL((k_pnode<4, MODE, FM, VT>), dim3(nblocks((int64_t)n_nodes * 4)), dim3(NT), 0, st, n_nodes, ncn, pp, pc, pv, dinv, b, xin, c1, c2, d, xout); break;
-        case 8: hipLaunchKernelGGL((k_pnode<8, MODE, FM, VT>), dim3(nblocks((int64_t)n_nodes * 8)), dim3(NT), 0, st, n_nodes, ncn, pp, pc, pv, dinv, b, xin, c1, c2, d, xout); break;
-        case 16: hipLaunchKernelGGL((k_pnode<16, MODE, FM, VT>), dim3(nblocks((int64_t)n_nodes * 16)), dim3(NT), 0, st, n_nodes, ncn, pp, pc, pv, dinv, b, xin, c1, c2, d, xout); break;
-        default: hipLaunchKernelGGL((k_pnode<32, MODE, FM, VT>), dim3(nblocks((int64_t)n_nodes * 32)), dim3(NT), 0, st, n_nodes, ncn, pp, pc, pv, dinv, b, xin, c1, c2, d, xout); break;
-    }
+    with_lanes<4, 32>(G, [&](auto L) {
+        hipLaunchKernelGGL((k_pnode<L(), MODE, FM, VT>), dim3(nblocks((int64_t)n_nodes * L())), dim3(NT), 0, st, n_nodes, ncn, pp, pc, pv, dinv, b, xin, c1, c2, d, xout);
+    });
 }
 template <int MODE, typename VT>
 static void launch_pnode_t(hipStream_t st, int fm, int G, int n_nodes, int ncn, const int32_t* pp, const int32_t* pc, const VT* pv,
@@ -976,15 +945,9 @@ static void launch_phi_rhs(knp_ctx* ctx, const double* r, const double* z, doubl
         hipLaunchKernelGGL(k_ion_charge, dim3(std::min(nblocks(n), 4096)), dim3(NT), 0, ctx->stream, n, ctx->z[0], ctx->z[1], ctx->z[2], z, ctx->d_w2);
         sc = ctx->d_w2;
     }
-#define KNP_PR(GG) hipLaunchKernelGGL((k_phi_rhs<GG, COMPACT>), dim3(nblocks((int64_t)n * GG)), dim3(NT), 0, ctx->stream, n, ctx->z[0], ctx->z[1], ctx->z[2], ctx->d_pair_ptr, ctx->d_pair_col, ctx->d_pair_M, r, z, sc, t)
-    switch (G) {
-        case 2: KNP_PR(2); break;
-        case 4: KNP_PR(4); break;
-        case 8: KNP_PR(8); break;
-        case 16: KNP_PR(16); break;
-        default: KNP_PR(32); break;
-    }
-#undef KNP_PR
+    with_lanes<2, 32>(G, [&](auto L) {
+        hipLaunchKernelGGL((k_phi_rhs<L(), COMPACT>), dim3(nblocks((int64_t)n * L())), dim3(NT), 0, ctx->stream, n, ctx->z[0], ctx->z[1], ctx->z[2], ctx->d_pair_ptr, ctx->d_pair_col, ctx->d_pair_M, r, z, sc, t);
+    });
 }
 // Literal block lower-triangular form (the reference's P with use_block_jacobi=False, KNPEMIx_problem.py:720-722: the phi rows
 // of P keep their -D grad k flux, i.e. P_{phi,kj} = dt z_j D_j K = the (phi,k) block of A): t_phi = r_phi - P_{phi,k} z_k
@@ -1025,14 +988,9 @@ template <bool COMPACT>
 static void launch_phi_rhs_literal(knp_ctx* ctx, const double* r, const double* z, double* t) {
     const int n = ctx->g.n_nodes_owned, G = ctx->pc_group;
     if (n <= 0) return;
-#define KNP_PL(GG) hipLaunchKernelGGL((k_phi_rhs_literal<GG, COMPACT>), dim3(nblocks((int64_t)n * GG)), dim3(NT), 0, ctx->stream, n, ctx->d_pair_ptr, ctx->d_pair_col, ctx->d_ac, r, z, t)
-    switch (G) {
-        case 4: KNP_PL(4); break;
-        case 8: KNP_PL(8); break;
-        case 16: KNP_PL(16); break;
-        default: KNP_PL(32); break;
-    }
-#undef KNP_PL
+    with_lanes<4, 32>(G, [&](auto L) {
+        hipLaunchKernelGGL((k_phi_rhs_literal<L(), COMPACT>), dim3(nblocks((int64_t)n * L())), dim3(NT), 0, ctx->stream, n, ctx->d_pair_ptr, ctx->d_pair_col, ctx->d_ac, r, z, t);
+    });
 }
 __global__ void __launch_bounds__(NT) k_schur_fin(int n_nodes, const double* __restrict__ cc, const double* __restrict__ t,
                                                   const double* __restrict__ w, double* __restrict__ z) {
@@ -1056,14 +1014,9 @@ template <int MODE, int TAG, typename VT>
 static void launch_spmv_t(hipStream_t st, int lanes, int n_rows, const int32_t* rp, const int32_t* ci,
                           const VT* v, const double* x, const double* b, double* y) {
     if (n_rows <= 0) return;
-    switch (lanes) {
-        case 2: hipLaunchKernelGGL((k_spmv<2, MODE, TAG, VT>), dim3(nblocks((int64_t)n_rows * 2)), dim3(NT), 0, st, n_rows, rp, ci, v, x, b, y); break;
-        case 4: hipLaunchKernelGGL((k_spmv<4, MODE, TAG, VT>), dim3(nblocks((int64_t)n_rows * 4)), dim3(NT), 0, st, n_rows, rp, ci, v, x, b, y); break;
-        case 8: hipLaunchKernelGGL((k_spmv<8, MODE, TAG, VT>), dim3(nblocks((int64_t)n_rows * 8)), dim3(NT), 0, st, n_rows, rp, ci, v, x, b, y); break;
-        case 16: hipLaunchKernelGGL((k_spmv<16, MODE, TAG, VT>), dim3(nblocks((int64_t)n_rows * 16)), dim3(NT), 0, st, n_rows, rp, ci, v, x, b, y); break;
-        case 32: hipLaunchKernelGGL((k_spmv<32, MODE, TAG, VT>), dim3(nblocks((int64_t)n_rows * 32)), dim3(NT), 0, st, n_rows, rp, ci, v, x, b, y); break;
-        default: hipLaunchKernelGGL((k_spmv<64, MODE, TAG, VT>), dim3(nblocks((int64_t)n_rows * 64)), dim3(NT), 0, st, n_rows, rp, ci, v, x, b, y); break;
-    }
+    with_lanes<2, 64>(lanes, [&](auto L) {
+        hipLaunchKernelGGL((k_spmv<L(), MODE, TAG, VT>), dim3(nblocks((int64_t)n_rows * L())), dim3(NT), 0, st, n_rows, rp, ci, v, x, b, y);
+    });
 }
 template <int MODE, int TAG = 0>
 static void launch_spmv(hipStream_t st, int lanes, int n_rows, const int32_t* rp, const int32_t* ci,
@@ -1098,12 +1051,9 @@ template <typename VT>
 static void launch_prolong_rows_t(hipStream_t st, int lanes, int n_act, const int32_t* rows, const int32_t* rp, const int32_t* ci,
                                   const VT* v, const double* x, double* y) {
     if (n_act <= 0) return;
-    switch (lanes) {
-        case 2: hipLaunchKernelGGL((k_prolong_rows<2, VT>), dim3(nblocks((int64_t)n_act * 2)), dim3(NT), 0, st, n_act, rows, rp, ci, v, x, y); break;
-        case 4: hipLaunchKernelGGL((k_prolong_rows<4, VT>), dim3(nblocks((int64_t)n_act * 4)), dim3(NT), 0, st, n_act, rows, rp, ci, v, x, y); break;
-        case 8: hipLaunchKernelGGL((k_prolong_rows<8, VT>), dim3(nblocks((int64_t)n_act * 8)), dim3(NT), 0, st, n_act, rows, rp, ci, v, x, y); break;
-        default: hipLaunchKernelGGL((k_prolong_rows<16, VT>), dim3(nblocks((int64_t)n_act * 16)), dim3(NT), 0, st, n_act, rows, rp, ci, v, x, y); break;
-    }
+    with_lanes<2, 16>(lanes, [&](auto L) {
+        hipLaunchKernelGGL((k_prolong_rows<L(), VT>), dim3(nblocks((int64_t)n_act * L())), dim3(NT), 0, st, n_act, rows, rp, ci, v, x, y);
+    });
 }
 
 // Restriction fused with the first Chebyshev step of the coarse level (zero initial guess):
@@ -1131,14 +1081,9 @@ template <typename VT>
 static void launch_restrict_first_t(hipStream_t st, int lanes, int n_rows, const int32_t* rp, const int32_t* ci, const VT* v,
                                     const double* x, double* y, double c, const double* dinv, double* d, double* xo) {
     if (n_rows <= 0) return;
-    switch (lanes) {
-        case 2: hipLaunchKernelGGL((k_restrict_first<2, VT>), dim3(nblocks((int64_t)n_rows * 2)), dim3(NT), 0, st, n_rows, rp, ci, v, x, y, c, dinv, d, xo); break;
-        case 4: hipLaunchKernelGGL((k_restrict_first<4, VT>), dim3(nblocks((int64_t)n_rows * 4)), dim3(NT), 0, st, n_rows, rp, ci, v, x, y, c, dinv, d, xo); break;
-        case 8: hipLaunchKernelGGL((k_restrict_first<8, VT>), dim3(nblocks((int64_t)n_rows * 8)), dim3(NT), 0, st, n_rows, rp, ci, v, x, y, c, dinv, d, xo); break;
-        case 16: hipLaunchKernelGGL((k_restrict_first<16, VT>), dim3(nblocks((int64_t)n_rows * 16)), dim3(NT), 0, st, n_rows, rp, ci, v, x, y, c, dinv, d, xo); break;
-        case 32: hipLaunchKernelGGL((k_restrict_first<32, VT>), dim3(nblocks((int64_t)n_rows * 32)), dim3(NT), 0, st, n_rows, rp, ci, v, x, y, c, dinv, d, xo); break;
-        default: hipLaunchKernelGGL((k_restrict_first<64, VT>), dim3(nblocks((int64_t)n_rows * 64)), dim3(NT), 0, st, n_rows, rp, ci, v, x, y, c, dinv, d, xo); break;
-    }
+    with_lanes<2, 64>(lanes, [&](auto L) {
+        hipLaunchKernelGGL((k_restrict_first<L(), VT>), dim3(nblocks((int64_t)n_rows * L())), dim3(NT), 0, st, n_rows, rp, ci, v, x, y, c, dinv, d, xo);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1242,13 +1187,9 @@ template <int FM, typename VT>
 static void launch_l0_down_t(hipStream_t st, int G, int n_nodes, const int32_t* pp, const int32_t* pc, const VT* pt, const double* b, double c, double* r,
                              const int32_t* nodes = nullptr) {
     if (n_nodes <= 0) return;
-    switch (G) {
-        case 2: hipLaunchKernelGGL((k_l0_down<2, FM, VT>), dim3(nblocks((int64_t)n_nodes * 2)), dim3(NT), 0, st, n_nodes, pp, pc, pt, b, c, r, nodes); break;
-        case 4: hipLaunchKernelGGL((k_l0_down<4, FM, VT>), dim3(nblocks((int64_t)n_nodes * 4)), dim3(NT), 0, st, n_nodes, pp, pc, pt, b, c, r, nodes); break;
-        case 8: hipLaunchKernelGGL((k_l0_down<8, FM, VT>), dim3(nblocks((int64_t)n_nodes * 8)), dim3(NT), 0, st, n_nodes, pp, pc, pt, b, c, r, nodes); break;
-        case 16: hipLaunchKernelGGL((k_l0_down<16, FM, VT>), dim3(nblocks((int64_t)n_nodes * 16)), dim3(NT), 0, st, n_nodes, pp, pc, pt, b, c, r, nodes); break;
-        default: hipLaunchKernelGGL((k_l0_down<32, FM, VT>), dim3(nblocks((int64_t)n_nodes * 32)), dim3(NT), 0, st, n_nodes, pp, pc, pt, b, c, r, nodes); break;
-    }
+    with_lanes<2, 32>(G, [&](auto L) {
+        hipLaunchKernelGGL((k_l0_down<L(), FM, VT>), dim3(nblocks((int64_t)n_nodes * L())), dim3(NT), 0, st, n_nodes, pp, pc, pt, b, c, r, nodes);
+    });
 }
 template <typename VT>
 static void launch_l0_down(hipStream_t st, int fm, int G, int n_nodes, const int32_t* pp, const int32_t* pc, const VT* pt, const double* b, double c, double* r,
@@ -1299,16 +1240,9 @@ static void launch_level_up_t(hipStream_t st, int lanes, int n_act, const int32_
                               const double* xc, const double* dinv, const double* b, const double* r, const double* xin, double c, double c2,
                               double* z, const double* cc) {
     if (n_act <= 0) return;
-#define KNP_UP(LL) hipLaunchKernelGGL((k_level_up<LL, VT, MODE>), dim3(nblocks((int64_t)n_act * LL)), dim3(NT), 0, st, n_act, rows, rp, ci, v, xc, dinv, b, r, xin, c, c2, z, cc)
-    switch (lanes) {
-        case 2: KNP_UP(2); break;
-        case 4: KNP_UP(4); break;
-        case 8: KNP_UP(8); break;
-        case 16: KNP_UP(16); break;
-        case 32: KNP_UP(32); break;
-        default: KNP_UP(64); break;
-    }
-#undef KNP_UP
+    with_lanes<2, 64>(lanes, [&](auto L) {
+        hipLaunchKernelGGL((k_level_up<L(), VT, MODE>), dim3(nblocks((int64_t)n_act * L())), dim3(NT), 0, st, n_act, rows, rp, ci, v, xc, dinv, b, r, xin, c, c2, z, cc);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1481,20 +1415,12 @@ k_blevel_up(int n_rows, const int32_t* __restrict__ rp, const float4* __restrict
         }
     }
 }
-#define KNP_BL_SWITCH(LANES, CALL) \
-    switch (LANES) {               \
-        case 2: CALL(2); break;    \
-        case 4: CALL(4); break;    \
-        case 8: CALL(8); break;    \
-        case 16: CALL(16); break;  \
-        default: CALL(32); break;  \
-    }
 template <int NF, int XS>
 static void launch_brestrict_t(hipStream_t st, const KnpBlockedCsr& M, const double* x, double* y, double c, const double* dinv, double* d, double* xo) {
     if (M.n_rows <= 0) return;
-#define KNP_BR(LL) hipLaunchKernelGGL((k_brestrict<LL, NF, XS>), dim3(nblocks((int64_t)M.n_rows * LL)), dim3(NT), 0, st, M.n_rows, M.rp, M.ev, M.ci, x, y, c, dinv, d, xo)
-    KNP_BL_SWITCH(M.lanes, KNP_BR)
-#undef KNP_BR
+    with_lanes<2, 32>(M.lanes, [&](auto L) {
+        hipLaunchKernelGGL((k_brestrict<L(), NF, XS>), dim3(nblocks((int64_t)M.n_rows * L())), dim3(NT), 0, st, M.n_rows, M.rp, M.ev, M.ci, x, y, c, dinv, d, xo);
+    });
 }
 static void launch_brestrict(hipStream_t st, int nf, int xs, const KnpBlockedCsr& M, const double* x, double* y, double c, const double* dinv, double* d, double* xo) {
     if (nf == 4) launch_brestrict_t<4, 4>(st, M, x, y, c, dinv, d, xo);
@@ -1504,17 +1430,17 @@ static void launch_brestrict(hipStream_t st, int nf, int xs, const KnpBlockedCsr
 template <int NF>
 static void launch_bresidual_t(hipStream_t st, const KnpBlockedCsr& M, const double* x, const double* b, double* y) {
     if (M.n_rows <= 0) return;
-#define KNP_BA(LL) hipLaunchKernelGGL((k_bresidual<LL, NF>), dim3(nblocks((int64_t)M.n_rows * LL)), dim3(NT), 0, st, M.n_rows, M.rp, M.ev, M.ci, x, b, y)
-    KNP_BL_SWITCH(M.lanes, KNP_BA)
-#undef KNP_BA
+    with_lanes<2, 32>(M.lanes, [&](auto L) {
+        hipLaunchKernelGGL((k_bresidual<L(), NF>), dim3(nblocks((int64_t)M.n_rows * L())), dim3(NT), 0, st, M.n_rows, M.rp, M.ev, M.ci, x, b, y);
+    });
 }
 template <int NF, int RS>
 static void launch_blevel_up_t(hipStream_t st, const KnpBlockedCsr& M, const double* xc, const double* dinv, const double* b, const double* r,
                                const double* xin, double c, double c2, double* z) {
     if (M.n_rows <= 0) return;
-#define KNP_BU(LL) hipLaunchKernelGGL((k_blevel_up<LL, NF, RS>), dim3(nblocks((int64_t)M.n_rows * LL)), dim3(NT), 0, st, M.n_rows, M.rp, M.ev, M.ci, xc, dinv, b, r, xin, c, c2, z)
-    KNP_BL_SWITCH(M.lanes, KNP_BU)
-#undef KNP_BU
+    with_lanes<2, 32>(M.lanes, [&](auto L) {
+        hipLaunchKernelGGL((k_blevel_up<L(), NF, RS>), dim3(nblocks((int64_t)M.n_rows * L())), dim3(NT), 0, st, M.n_rows, M.rp, M.ev, M.ci, xc, dinv, b, r, xin, c, c2, z);
+    });
 }
 static void launch_blevel_up(hipStream_t st, int nf, int rs, const KnpBlockedCsr& M, const double* xc, const double* dinv, const double* b, const double* r,
                              const double* xin, double c, double c2, double* z) {
@@ -1629,20 +1555,14 @@ k_blevel_up_dots(int n_rows, const int32_t* __restrict__ rp, const float4* __res
 // taken here (more than RED_WIDE blocks: the bandwidth-bound sizes, where a launch less does not matter; the plain leg then runs)
 static bool launch_blevel_up_dots(knp_ctx* ctx, hipStream_t st, const KnpBlockedCsr& M, const double* xc, const double* dinv, const double* b,
                                   const double* r, double c, double c2, double* z, DotReq* dq) {
-    const int lanes = M.lanes == 2 || M.lanes == 4 || M.lanes == 8 || M.lanes == 16 ? M.lanes : 32;   // as KNP_BL_SWITCH
+    const int lanes = clamp_lanes<2, 32>(M.lanes);   // the width with_lanes<2, 32> runs below
     const int64_t threads = (int64_t)M.n_rows * lanes;
     if (M.n_rows <= 0 || dq->m < 0 || dq->m > BU_MAX_M || threads > (int64_t)RED_WIDE * NT) return false;
     const int nbd = nblocks(threads, NT);
-#define KNP_BUD_G(LL, NS_, G_) hipLaunchKernelGGL((k_blevel_up_dots<LL, NS_, G_>), dim3(nbd), dim3(NT), 0, st, M.n_rows, M.rp, M.ev, M.ci, xc, dinv, b, r, \
-                                              (const double*)nullptr, c, c2, z, dq->m, dq->ldv, dq->V, dq->partial)
-#define KNP_BUD(LL)                                                                            \
-    do {                                                                                       \
-        if (dq->m <= 3) { if (dq->ns) KNP_BUD_G(LL, true, 3); else KNP_BUD_G(LL, false, 3); } \
-        else { if (dq->ns) KNP_BUD_G(LL, true, 8); else KNP_BUD_G(LL, false, 8); }            \
-    } while (0)
-    KNP_BL_SWITCH(M.lanes, KNP_BUD)
-#undef KNP_BUD
-#undef KNP_BUD_G
+    with_lanes<2, 32>(M.lanes, [&](auto L) { with_flag(dq->ns, [&](auto NS) { with_either<3, 8>(dq->m <= 3, [&](auto G) {
+        hipLaunchKernelGGL((k_blevel_up_dots<L(), NS(), G()>), dim3(nbd), dim3(NT), 0, st, M.n_rows, M.rp, M.ev, M.ci, xc, dinv, b, r,
+                           (const double*)nullptr, c, c2, z, dq->m, dq->ldv, dq->V, dq->partial);
+    }); }); });
     dq->done = true;
     dq->nb = nbd;
     ++ctx->n_fused_dots;
@@ -1780,7 +1700,7 @@ static bool launch_spmv_dots(knp_ctx* ctx, const double* x, const double* b, dou
     const int n_list = ctx->g.n_nodes_owned;
     const int G = ctx->spmv_group;
     if (!ctx->spmv_dots || !fin_ok(ctx) || ctx->halo || ctx->p2p || ctx->n_bc > 0 || ctx->d_pair_MK == nullptr || n_list <= 0 || m < 0 ||
-        m > BU_MAX_M || (G != 4 && G != 8 && G != 16 && G != 32))
+        m > BU_MAX_M || clamp_lanes<4, 32>(G) != G)
         return false;
     const int nbd = nblocks((int64_t)n_list * G);
     if (nbd > SPMV_WIDE) return false;
@@ -1794,23 +1714,13 @@ static bool launch_spmv_dots(knp_ctx* ctx, const double* x, const double* b, dou
         eb = prof_event(ctx);
         if (!ea || !eb) ea = eb = nullptr;
     }
-#define KNP_SD4(GG, MO, UU, GVV)                                                                                                         \
-    hipExtLaunchKernelGGL((k_spmv_node_dots<GG, MO, true, UU, GVV>), dim3(nbd), dim3(NT), 0, ctx->stream, ea, eb, 0, n_list, ctx->d_pair_ptr, \
-                          ctx->d_pair_col, ctx->d_ac, ctx->d_pair_MK, ci, ce, ctx->d_at, ctx->d_node_gv, ctx->d_node_side, ctx->d_gptr, ctx->d_gx_i, \
-                          ctx->d_gx_e, ctx->d_ax, x, b, y, m, ldv, V, ctx->d_partial)
-#define KNP_SD3(GG, MO, UU) do { if (m <= 3) KNP_SD4(GG, MO, UU, 3); else KNP_SD4(GG, MO, UU, 8); } while (0)
-#define KNP_SD2(GG, MO) do { if (unroll >= 2) KNP_SD3(GG, MO, 2); else KNP_SD3(GG, MO, 1); } while (0)
-#define KNP_SD(GG) do { if (b) KNP_SD2(GG, 1); else KNP_SD2(GG, 0); } while (0)
-    switch (G) {
-        case 4: KNP_SD(4); break;
-        case 8: KNP_SD(8); break;
-        case 16: KNP_SD(16); break;
-        default: KNP_SD(32); break;
-    }
-#undef KNP_SD
-#undef KNP_SD2
-#undef KNP_SD3
-#undef KNP_SD4
+    with_lanes<4, 32>(G, [&](auto L) { with_flag(b != nullptr, [&](auto RES) {   // residual form (MODE 1) when b is given
+    with_either<1, 2>(unroll < 2, [&](auto U) { with_either<3, 8>(m <= 3, [&](auto GV) {
+        hipExtLaunchKernelGGL((k_spmv_node_dots<L(), RES() ? 1 : 0, true, U(), GV()>), dim3(nbd), dim3(NT), 0, ctx->stream, ea, eb, 0, n_list, ctx->d_pair_ptr,
+                              ctx->d_pair_col, ctx->d_ac, ctx->d_pair_MK, ci, ce, ctx->d_at, ctx->d_node_gv, ctx->d_node_side, ctx->d_gptr, ctx->d_gx_i,
+                              ctx->d_gx_e, ctx->d_ax, x, b, y, m, ldv, V, ctx->d_partial);
+    }); });
+    }); });
     if (ea && eb) ctx->prof_recs.push_back({ea, eb, 0});
     ++ctx->n_spmv_dots;
     *nb_out = nbd;
@@ -2440,14 +2350,9 @@ template <typename VT>
 static void launch_cheby_t(hipStream_t st, int lanes, int n_rows, const int32_t* rp, const int32_t* ci, const VT* v,
                            const double* dinv, const double* b, const double* xin, double c1, double c2, double* d, double* xout) {
     if (n_rows <= 0) return;
-    switch (lanes) {
-        case 2: hipLaunchKernelGGL((k_cheby_step<2, VT>), dim3(nblocks((int64_t)n_rows * 2)), dim3(NT), 0, st, n_rows, rp, ci, v, dinv, b, xin, c1, c2, d, xout); break;
-        case 4: hipLaunchKernelGGL((k_cheby_step<4, VT>), dim3(nblocks((int64_t)n_rows * 4)), dim3(NT), 0, st, n_rows, rp, ci, v, dinv, b, xin, c1, c2, d, xout); break;
-        case 8: hipLaunchKernelGGL((k_cheby_step<8, VT>), dim3(nblocks((int64_t)n_rows * 8)), dim3(NT), 0, st, n_rows, rp, ci, v, dinv, b, xin, c1, c2, d, xout); break;
-        case 16: hipLaunchKernelGGL((k_cheby_step<16, VT>), dim3(nblocks((int64_t)n_rows * 16)), dim3(NT), 0, st, n_rows, rp, ci, v, dinv, b, xin, c1, c2, d, xout); break;
-        case 32: hipLaunchKernelGGL((k_cheby_step<32, VT>), dim3(nblocks((int64_t)n_rows * 32)), dim3(NT), 0, st, n_rows, rp, ci, v, dinv, b, xin, c1, c2, d, xout); break;
-        default: hipLaunchKernelGGL((k_cheby_step<64, VT>), dim3(nblocks((int64_t)n_rows * 64)), dim3(NT), 0, st, n_rows, rp, ci, v, dinv, b, xin, c1, c2, d, xout); break;
-    }
+    with_lanes<2, 64>(lanes, [&](auto L) {
+        hipLaunchKernelGGL((k_cheby_step<L(), VT>), dim3(nblocks((int64_t)n_rows * L())), dim3(NT), 0, st, n_rows, rp, ci, v, dinv, b, xin, c1, c2, d, xout);
+    });
 }
 static void launch_cheby(hipStream_t st, int lanes, int n_rows, const int32_t* rp, const int32_t* ci, const double* v, const float* vf,
                          const double* dinv, const double* b, const double* xin, double c1, double c2, double* d, double* xout) {
@@ -3620,18 +3525,13 @@ int knp_assemble_rhs(knp_ctx* ctx, const knp_fields* fields, double* b) {
     for (int j = 0; j < 3; ++j) { src.ki[j] = ctx->src_i[j]; src.ke[j] = ctx->src_e[j]; }
     src.phim = nullptr;
     for (int k = 0; k < KNP_MAX_AUX; ++k) src.aux[k] = nullptr;
-#define KNP_RHS(GG) hipLaunchKernelGGL((k_rhs<GG>), dim3(nblocks((int64_t)g.n_nodes_owned * GG)), dim3(NT), 0, ctx->stream, g.n_nodes_owned, g.n_g, g.dim, ctx->dt, \
-                                       ctx->d_node_vertex, ctx->d_node_side, ctx->d_pair_ptr, ctx->d_pair_col, ctx->d_pair_M, f, src,                     \
-                                       ctx->have_sources ? 1 : 0, ctx->d_node_gv, ctx->d_gdiag, ctx->d_gcptr, ctx->d_gc_facet, ctx->d_gc_lab, ctx->d_fvec, b)
     if (g.n_nodes_owned > 0) {
-        switch (ctx->pc_group) {
-            case 4: KNP_RHS(4); break;
-            case 8: KNP_RHS(8); break;
-            case 16: KNP_RHS(16); break;
-            default: KNP_RHS(32); break;
-        }
+        with_lanes<4, 32>(ctx->pc_group, [&](auto G) {
+            hipLaunchKernelGGL((k_rhs<G()>), dim3(nblocks((int64_t)g.n_nodes_owned * G())), dim3(NT), 0, ctx->stream, g.n_nodes_owned, g.n_g, g.dim, ctx->dt,
+                               ctx->d_node_vertex, ctx->d_node_side, ctx->d_pair_ptr, ctx->d_pair_col, ctx->d_pair_M, f, src,
+                               ctx->have_sources ? 1 : 0, ctx->d_node_gv, ctx->d_gdiag, ctx->d_gcptr, ctx->d_gc_facet, ctx->d_gc_lab, ctx->d_fvec, b);
+        });
     }
-#undef KNP_RHS
     launch_schur_diag(ctx, f);   // before a possible knp_gmres_prepare forks the side stream (it reads d_cc)
     HIPCHK(hipGetLastError());
     return KNP_OK;
