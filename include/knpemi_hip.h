@@ -28,6 +28,9 @@
  *                                    (KNPEMIx_solver.py:177-209, 452-468)
  *   knp_hh_update                    HodgkinHuxley.update_gating_variables
  *                                    (KNPEMIx_ionic_model.py:605-671)
+ *   knp_state_reset / knp_state_set_program / knp_state_set_constants / knp_state_update
+ *        the same update for the states of any mechanism: the gating ODEs of KNPEMIx_ionic_model.py:605-671 with the rate
+ *        functions given as bytecode programs instead of the six hard-coded ones
  *   knp_l2_norms                     assemble_scalar(inner(phi,phi)*dx(tag)) (src/CGx/KNPEMI/main.py:70-84)
  *   knp_diag_set_cell_tags / knp_diag_volume_integrals
  *        assemble_scalar(k*dx(tag)) per ion and cell tag of print_conservation (KNPEMIx_problem.py:821-840)
@@ -71,6 +74,8 @@ extern "C" {
 #define KNP_MAX_AUX 8
 #define KNP_DIAG_MAX_CONSTS 64   /* constants of a diagnostic program (knp_diag_set_program) */
 #define KNP_MAX_PROG_REGS 48
+#define KNP_STATE_MAX_INSTR 768  /* instructions of all state programs together (knp_state_set_program) */
+#define KNP_STATE_MAX_CONSTS 128 /* constants of all state programs together */
 #define KNP_MAX_AMG_LEVELS 16
 
 #define KNP_OK 0
@@ -355,6 +360,35 @@ int knp_pack(knp_ctx* ctx, const knp_fields_out* fields, double* x);
 int knp_unpack(knp_ctx* ctx, const double* x, const knp_fields_out* fields);
 int knp_hh_update(knp_ctx* ctx, const double* phi_m, double* n, double* m, double* h, int32_t count,
                   double dt, double phi_rest, int32_t rush_larsen, int32_t substeps);
+/* Membrane state variables: nodal fields that a mechanism declares and the library advances after every solve.  Every state is one
+ * bytecode program (the opcodes and limits of knp_set_program) that reads phi_m, the concentrations, the coordinates, constants and the
+ * aux fields -- among them the states themselves, each under the aux slot given for it.  This is HodgkinHuxley.update_gating_variables
+ * (KNPEMIx_ionic_model.py:605-671) with the rates handed in: alpha_n .. beta_h there (:617-622) are the OUT 0 / OUT 1 of three gates.
+ * knp_state_reset: forget all state programs and make room for n_states of them, 0 .. KNP_MAX_AUX (the reference's Function(V) per
+ *   gate in HodgkinHuxley._init, :470-480).  Synchronous.
+ * knp_state_set_program: the program of state `slot`.  kind 0, a gate dy/dt = alpha (1 - y) - beta y: KNP_OP_OUT 0 = alpha,
+ *   KNP_OP_OUT 1 = beta (the rate expressions of :617-622).  kind 1, a general state: KNP_OP_OUT 0 = dy/dt.  aux_index: the aux slot
+ *   under which programs read this state (one state per slot).  All programs together hold at most KNP_STATE_MAX_INSTR instructions and
+ *   KNP_STATE_MAX_CONSTS constants.  Host only; the code is uploaded by the next knp_state_update.
+ * knp_state_set_constants: new constants for the program of `slot`, same count (the per-step refresh of a time-dependent
+ *   dfx.fem.Constant).  They travel as kernel arguments of the next update: no copy, no synchronisation.
+ * knp_state_update: one PDE step of all states at the vertices 0 .. count-1 (count <= the local vertices, ghosts included, as
+ *   knp_hh_update; no communication), enqueued.  state[s] is the device buffer of slot s; fields->phi_m is read, fields->k_i / k_e only
+ *   when a program reads a concentration (null there is then KNP_E_ARG), fields->aux[k] for the slots that are not states (null reads as
+ *   0).  Gates: alpha, beta evaluated once from the values at the start of the step, then y <- y_inf + (y - y_inf) exp(-dt (alpha + beta))
+ *   (rush_larsen; the sub-steps collapse, :640-655; a vertex where alpha + beta == 0 keeps its y) or `substeps` forward-Euler steps y += dto alpha (1 - y) - dto beta y (:656-671).
+ *   General states: `substeps` forward-Euler steps, the program evaluated again in each; within a sub-step every program reads the
+ *   states as they stood at its beginning.  With rush_larsen the gates keep their start-of-step value until the end of the step.
+ *   The same inputs give the same bits on every run.
+ * Errors: KNP_E_ARG for a slot outside 0 .. n_states-1, a kind other than 0 / 1, an aux_index outside 0 .. KNP_MAX_AUX-1 or taken by
+ *   another state, an invalid or too long program, a constant count mismatch, a null pointer, count < 0 or beyond the local vertices,
+ *   dt <= 0, substeps < 1; KNP_E_STATE for an update with no states or a slot without a program.  Nothing is launched then. */
+int knp_state_reset(knp_ctx* ctx, int32_t n_states);
+int knp_state_set_program(knp_ctx* ctx, int32_t slot, int32_t kind /* 0 gate, 1 general */, int32_t aux_index, int32_t n_instr,
+                          const int32_t* code /* host [n_instr*4] */, int32_t n_consts, const double* consts /* host */);
+int knp_state_set_constants(knp_ctx* ctx, int32_t slot, int32_t n_consts, const double* consts /* host */);
+int knp_state_update(knp_ctx* ctx, const knp_fields* fields, double* const* state /* host [n_states] device pointers */, int32_t count,
+                     double dt, int32_t rush_larsen, int32_t substeps);
 int knp_l2_norms(knp_ctx* ctx, const double* phi_i, const double* phi_e, double* out /* host [2]: squared, owned cells */);
 /* Per-tag diagnostics.  A tag map lists items sorted by a dense tag index: seg_ptr[t] .. seg_ptr[t+1]-1 are the positions of tag t in
  * `cells` / `facets`; seg_ptr[0] == 0, non-decreasing; every item at most once.  The maps are uploaded once (synchronous); the

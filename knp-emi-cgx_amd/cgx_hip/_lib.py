@@ -15,6 +15,8 @@ KNP_MAX_IONS = 3
 KNP_MAX_AUX = 8
 KNP_MAX_PROG_REGS = 48
 KNP_DIAG_MAX_CONSTS = 64
+KNP_STATE_MAX_INSTR = 768
+KNP_STATE_MAX_CONSTS = 128
 KNP_SZ_COUNT = 16
 (SZ_N_NODES, SZ_N_NODES_OWNED, SZ_N_DOF_LOCAL, SZ_N_DOF_OWNED, SZ_NNZ, SZ_N_PAIRS, SZ_N_CONTRIB,
  SZ_N_GAMMA_VERTS, SZ_N_GAMMA_PAIRS, SZ_NNZ_P, SZ_N_PHI_OWNED, SZ_NNZ_P_PHI, SZ_EMI_NNZ) = range(13)
@@ -117,6 +119,10 @@ SIGNATURES = {
     "knp_pack": (C.c_int, [vp, C.POINTER(FieldsOut), vp]),
     "knp_unpack": (C.c_int, [vp, vp, C.POINTER(FieldsOut)]),
     "knp_hh_update": (C.c_int, [vp, vp, vp, vp, vp, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32]),
+    "knp_state_reset": (C.c_int, [vp, C.c_int32]),
+    "knp_state_set_program": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p, C.c_int32, f64p]),
+    "knp_state_set_constants": (C.c_int, [vp, C.c_int32, C.c_int32, f64p]),
+    "knp_state_update": (C.c_int, [vp, C.POINTER(Fields), C.POINTER(vp), C.c_int32, C.c_double, C.c_int32, C.c_int32]),
     "knp_l2_norms": (C.c_int, [vp, vp, vp, f64p]),
     "knp_diag_set_cell_tags": (C.c_int, [vp, C.c_int32, i32p, i32p]),
     "knp_diag_volume_integrals": (C.c_int, [vp, C.POINTER(Fields), vp]),

@@ -29,7 +29,43 @@ def _i32(a):
     return a.ctypes.data_as(_lib.i32p)
 
 
-class Backend:
+class StateUpdate:
+    """The state variables of the problem's mechanisms on a backend (``self.p.state_variables``, csrc/knp_states.inc).  Every
+    knp_state_* call is counted in ``state_calls``: a problem without states makes none."""
+
+    state_calls = 0
+
+    def _state_call(self, fn, *args):
+        self.state_calls += 1
+        self.check(fn(self.ctx, *args))
+
+    def state_setup(self):
+        """hand the compiled state programs over (after every compilation)"""
+        states = self.p.state_variables
+        self._state_call(self.lib.knp_state_reset, len(states))
+        for s, st in enumerate(states):
+            code = np.ascontiguousarray(st.spec.code, dtype=np.int32)
+            consts = st.spec.constants()
+            self._state_call(self.lib.knp_state_set_program, s, int(st.kind), int(st.aux_index), code.shape[0], _i32(code), consts.shape[0],
+                             _f64(consts) if consts.size else None)
+        self._state_ptrs = (C.c_void_p * max(len(states), 1))(*[st.function.data_ptr() for st in states])
+
+    def state_update(self):
+        """one PDE step of all states at every local vertex (enqueued); the programs' constants are refreshed first"""
+        p = self.p
+        states = p.state_variables
+        for s, st in enumerate(states):
+            consts = st.spec.constants()
+            if consts.size:
+                self._state_call(self.lib.knp_state_set_constants, s, consts.shape[0], _f64(consts))
+        f = self.fields()
+        for s, st in enumerate(states):      # the currents read a state where the update writes it
+            assert f.aux[st.aux_index] == st.function.data_ptr() == self._state_ptrs[s], f"state '{st.name}' moved after the fields were built"
+        self._state_call(self.lib.knp_state_update, C.byref(f), self._state_ptrs, int(states[0].function.x.array.numel()), float(p.dt.value),
+                         int(p.state_rush_larsen), int(p.state_substeps))
+
+
+class Backend(StateUpdate):
     def __init__(self, problem):
         self.p = problem
         self.lib = _lib.load()
@@ -108,6 +144,8 @@ class Backend:
             self.p2p_setup()
         if getattr(problem, "programs", None):
             self.upload_programs()
+        if getattr(problem, "state_variables", None) and all(st.spec is not None for st in problem.state_variables):
+            self.state_setup()      # else setup_variational_form() has not compiled them yet: it hands them over
         self.set_sources()
         self.setup_deflation()
         self.setup_dirichlet()

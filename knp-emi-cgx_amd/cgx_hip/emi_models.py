@@ -9,6 +9,7 @@ from abc import ABC, abstractmethod
 
 import numpy as np
 
+from . import fem
 from .fem import Constant, Function
 
 
@@ -25,6 +26,10 @@ def g_syn(t: float) -> float:
 
 
 class IonicModel(ABC):
+    # integration of the states a model declares with ``add_state``
+    use_Rush_Larsen = True
+    time_steps_ODE = 25
+
     def __init__(self, EMIx_problem, tags=None):
         self.problem = EMIx_problem
         self.tags = tags
@@ -41,11 +46,28 @@ class IonicModel(ABC):
     def _eval(self):
         ...
 
+    def add_state(self, name, init, alpha=None, beta=None, inf=None, tau=None, rhs=None):
+        """Declare a nodal state of this mechanism, from ``_init()``; returns its Function (filled with ``init``, a number or nodal
+        values) for use in ``_eval`` and in rate expressions.  One of
+          ``alpha=, beta=``  gate, dy/dt = alpha (1 - y) - beta y (where alpha + beta == 0 the gate keeps its value);
+          ``inf=, tau=``     the same gate with alpha = inf / tau, beta = (1 - inf) / tau;
+          ``rhs=``           general, dy/dt = rhs.
+        An expression may be a callable of the state's own Function (``rhs=lambda y: -y / tau``); it is called when the programs
+        are compiled, so it may name states that are declared later.
+        The expressions may read phi_M, SpatialCoordinate, Constants and any state.  ``update()`` advances the states on the GPU
+        (knp_state_update): gates with frozen rates, by the Rush-Larsen step or ``time_steps_ODE`` forward-Euler sub-steps
+        (``use_Rush_Larsen``); general states by forward-Euler sub-steps.  It is this class's ``update()`` that does so: a model
+        that overrides ``update()`` calls ``super().update()``, or its declared states never advance."""
+        return fem.declare_state(self, name, init, alpha=alpha, beta=beta, inf=inf, tau=tau, rhs=rhs).function
+
     def refresh(self, t: float):
         """time-dependent constants of the program, before the right-hand side of the step ending at ``t``"""
 
     def update(self):
-        """after the solve: advance the model's state with the new phi_M"""
+        """after the solve: advance the model's state with the new phi_M -- the declared states of all models in one launch.
+        An override keeps the declared states moving by calling ``super().update()`` (``HH_model`` declares none)."""
+        if getattr(self, "states", None):
+            self.problem.advance_states(self)
 
 
 class Passive_model(IonicModel):

@@ -22,6 +22,7 @@ import torch
 import yaml
 
 from . import _lib, fem
+from .backend import StateUpdate
 from . import mesh as meshmod
 from .emi_models import HH_model, IonicModel, Passive_model, g_syn_none
 from .fem import Function, FunctionSpace
@@ -40,7 +41,7 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-class EmiBackend:
+class EmiBackend(StateUpdate):
     """Owns the ``knp_ctx`` of an EMI problem and the device vectors b, x [n_nodes]."""
 
     def __init__(self, problem, gamma_prog):
@@ -141,9 +142,11 @@ class EmiBackend:
             p = self.p
             f = _lib.Fields()
             f.phi_m = p.phi_M.data_ptr()
-            if hasattr(p, "n"):
-                for k, fn in enumerate((p.n, p.m, p.h)):
-                    f.aux[k] = fn.data_ptr()
+            aux = getattr(p, "aux_functions", None)      # n, m, h when they exist, then the declared states (compile_programs)
+            if aux is None:
+                aux = (p.n, p.m, p.h) if hasattr(p, "n") else ()
+            for k, fn in enumerate(aux):
+                f.aux[k] = fn.data_ptr()
             self._fields = f
         return self._fields
 
@@ -327,10 +330,18 @@ class ProblemEMI(MixedDimensionalProblem):
         missing = sorted(set(self.gamma_tags) - tags)
         if self.ionic_models and missing:
             raise RuntimeError(f"Mismatch between membrane tags and ionic models tags: no model on membrane tags {missing}")
+        self.state_variables, self.state_rush_larsen, self.state_substeps = fem.collect_states(self.ionic_models)
         self.print("# Membrane tags = ", len(self.gamma_tags))
         self.print("# Ionic models  = ", len(self.ionic_models), "\n")
 
     init_ionic_models = init_ionic_model
+
+    def advance_states(self, model):
+        """``IonicModel.update()`` of a model with declared states: one launch advances the states of all models, at the call of
+        the first model that has any"""
+        owners = [m for m in self.ionic_models if getattr(m, "states", None)]
+        if owners and model is owners[0]:
+            self.backend.state_update()
 
     # ---- forms
     def setup_bilinear_form(self):
@@ -363,15 +374,26 @@ class ProblemEMI(MixedDimensionalProblem):
         self.print("Setting up linear form ...")
         assert self.backend is not None, "setup_bilinear_form() first"
         self.backend.upload_programs(self.compile_programs())
+        if self.state_variables:
+            self.backend.state_setup()
         self.L = "knp_emi_assemble_rhs"
 
     def compile_programs(self):
-        """one bytecode program per model: KNP_OP_PHIM, KNP_OP_AUX 0..2 (n, m, h), constants, KNP_OP_OUT 0"""
+        """one bytecode program per model: KNP_OP_PHIM, KNP_OP_AUX (n, m, h in 0..2 when they exist, then the declared states),
+        constants, KNP_OP_OUT 0; and one program per declared state"""
+        states = getattr(self, "state_variables", [])
         aux = [self.n, self.m, self.h] if hasattr(self, "n") else []
+        aux += [st.function for st in states if not any(st.function is f for f in aux)]
+        n_known = len(aux)
+        if n_known > _lib.KNP_MAX_AUX:
+            raise ValueError(f"more than {_lib.KNP_MAX_AUX} auxiliary nodal fields in membrane expressions")
         roles = {id(self.phi_M): ("PHIM", 0)}
         self.programs = [fem.compile_program([model._eval()], roles, aux_functions=aux) for model in self.ionic_models]
-        if len(aux) > 3:
-            raise ValueError("EMI membrane models may only read phi_M and the gating variables n, m, h")
+        for st in states:
+            fem.compile_state_program(st, roles, aux)
+        if len(aux) > n_known:
+            raise ValueError("EMI membrane models may only read phi_M, the gating variables n, m, h and the declared states")
+        self.aux_functions = aux
         return self.programs
 
     def setup_preconditioner(self):

@@ -296,6 +296,99 @@ def compile_program(outputs, field_roles, aux_functions=None):
 
 
 # ------------------------------------------------------------------------------------------
+# state variables of membrane mechanisms (IonicModel.add_state)
+# ------------------------------------------------------------------------------------------
+RESERVED_STATE_NAMES = frozenset({"t", "step", "l2g", "coords", "phi_m"})      # keys of a checkpoint besides the solution functions
+
+
+class StateVariable:
+    """A nodal state that a membrane mechanism declares and the library advances after every solve (knp_state_update).
+    ``kind`` 0: a gate dy/dt = alpha (1 - y) - beta y, ``exprs`` = (alpha, beta); ``kind`` 1: dy/dt = rhs, ``exprs`` = (rhs,).
+    ``spec`` / ``aux_index``: the compiled program and the aux slot of ``function``, set by ``compile_state_program``."""
+
+    def __init__(self, name, function, kind, build, model):
+        self.name, self.function, self.kind, self.model = name, function, kind, model
+        self._build, self._exprs = build, None
+        self.spec = None
+        self.aux_index = None
+
+    @property
+    def exprs(self):
+        """built at the first use -- the compilation, after every model's ``_init()`` -- so that callables may name any state"""
+        if self._exprs is None:
+            self._exprs = tuple(self._build())
+        return self._exprs
+
+
+def declare_state(model, name, init, alpha=None, beta=None, inf=None, tau=None, rhs=None):
+    """What ``IonicModel.add_state`` of both model families does: one of the forms (alpha, beta), (inf, tau) or rhs; the
+    Function lives on the problem's space ``V`` and starts from ``init`` (a number or nodal values).  Each expression may be a
+    callable ``y -> expression`` of the state's own Function instead.  It is called when the programs are compiled, so it may also
+    name states that are declared later: that is how a state reads itself or two states read each other."""
+    forms = {"alpha/beta": (alpha, beta), "inf/tau": (inf, tau), "rhs": (rhs,)}
+    begun = [k for k, v in forms.items() if any(x is not None for x in v)]
+    whole = [k for k, v in forms.items() if all(x is not None for x in v)]
+    if len(begun) != 1 or begun != whole:
+        raise ValueError(f"state '{name}': give exactly one of alpha= and beta=, inf= and tau=, or rhs= "
+                         f"(got {', '.join(begun) if begun else 'none'}{'' if begun == whole else ', incomplete'})")
+    p = model.problem
+    taken = RESERVED_STATE_NAMES | {g.name for side in getattr(p, "wh", []) for g in (side if isinstance(side, (list, tuple)) else [side])}
+    if str(name) in taken:
+        raise ValueError(f"state '{name}': the name is a key of the checkpoints already ({', '.join(sorted(taken))})")
+    f = Function(p.V, str(name))
+    vals = np.broadcast_to(np.asarray(init, dtype=np.float64), (f.x.array.numel(),))
+    f.x.array[:] = torch.as_tensor(vals.copy(), device=f.x.array.device)
+    ex = lambda e: as_expr(e(f) if callable(e) and not isinstance(e, Expr) else e)
+    if whole[0] == "alpha/beta":
+        kind, build = 0, lambda: (ex(alpha), ex(beta))
+    elif whole[0] == "inf/tau":      # the same gate: alpha = inf / tau, beta = (1 - inf) / tau; each expression built once
+        def build():
+            i, t = ex(inf), ex(tau)
+            return i / t, (1.0 - i) / t
+        kind = 0
+    else:
+        kind, build = 1, lambda: (ex(rhs),)
+    st = StateVariable(str(name), f, kind, build, model)
+    states = model.__dict__.setdefault("states", [])
+    states[:] = [s for s in states if s.name != st.name] + [st]       # a second _init() declares anew
+    return st
+
+
+def collect_states(models):
+    """The states of ``models`` in declaration order and the (use_Rush_Larsen, time_steps_ODE) their models agree on"""
+    states, owners = [], []
+    if sum(len(getattr(m, "states", [])) for m in models) > KNP_MAX_AUX:      # every state takes an aux slot
+        raise ValueError(f"more than {KNP_MAX_AUX} auxiliary nodal fields in membrane expressions")
+    for m in models:
+        for st in getattr(m, "states", []):
+            if any(st.name == o.name for o in states):
+                raise ValueError(f"state '{st.name}' is declared twice")
+            states.append(st)
+            if m not in owners:
+                owners.append(m)
+    settings = {(bool(getattr(m, "use_Rush_Larsen", True)), int(getattr(m, "time_steps_ODE", 25))) for m in owners}
+    if len(settings) > 1:
+        raise ValueError("the models that declare states disagree on use_Rush_Larsen / time_steps_ODE: "
+                         + ", ".join(f"{m}: {bool(getattr(m, 'use_Rush_Larsen', True))} / {int(getattr(m, 'time_steps_ODE', 25))}" for m in owners))
+    rl, sub = settings.pop() if settings else (True, 25)
+    if sub < 1:
+        raise ValueError("time_steps_ODE must be at least 1")
+    return states, rl, sub
+
+
+def compile_state_program(state, field_roles, aux_functions):
+    """One program per state through ``compile_program``: a gate writes KNP_OP_OUT 0 = alpha and KNP_OP_OUT 1 = beta, a general
+    state KNP_OP_OUT 0 = dy/dt.  The state's Function takes (or already has) a slot of the shared list ``aux_functions``."""
+    if not any(f is state.function for f in aux_functions):
+        if len(aux_functions) >= KNP_MAX_AUX:
+            raise ValueError(f"more than {KNP_MAX_AUX} auxiliary nodal fields in membrane expressions")
+        aux_functions.append(state.function)
+    state.aux_index = next(k for k, f in enumerate(aux_functions) if f is state.function)
+    state.spec = compile_program(list(state.exprs), field_roles, aux_functions)
+    return state.spec
+
+
+# ------------------------------------------------------------------------------------------
 # host evaluation (setup-time scalars such as the stimulus area; never on the timed path)
 # ------------------------------------------------------------------------------------------
 def evaluate_numpy(e, env):

@@ -23,6 +23,10 @@ from .fem import Constant, Function
 class IonicModel(ABC):
     """Base class (reference :11-75)."""
 
+    # integration of the states a model declares with ``add_state`` (the reference's HodgkinHuxley options, :430-436)
+    use_Rush_Larsen = True
+    time_steps_ODE = 25
+
     def __init__(self, KNPEMIx_problem, tags: tuple = None):
         self.problem = KNPEMIx_problem
         self.tags = tags
@@ -39,6 +43,19 @@ class IonicModel(ABC):
     @abstractmethod
     def _eval(self, ion_idx):
         pass
+
+    def add_state(self, name, init, alpha=None, beta=None, inf=None, tau=None, rhs=None):
+        """Declare a nodal state of this mechanism, from ``_init()``; returns its Function (filled with ``init``, a number or nodal
+        values) for use in ``_eval`` and in rate expressions.  One of
+          ``alpha=, beta=``  gate, dy/dt = alpha (1 - y) - beta y (where alpha + beta == 0 the gate keeps its value);
+          ``inf=, tau=``     the same gate with alpha = inf / tau, beta = (1 - inf) / tau;
+          ``rhs=``           general, dy/dt = rhs.
+        An expression may be a callable of the state's own Function (``rhs=lambda y: -y / tau``); it is called when the programs
+        are compiled, so it may name states that are declared later.
+        The expressions may read phi_m, the ion concentrations, SpatialCoordinate, Constants and any state.  After every solve
+        the library advances all states on the GPU (knp_state_update): gates with frozen rates, by the Rush-Larsen step or
+        ``time_steps_ODE`` forward-Euler sub-steps (``use_Rush_Larsen``); general states by forward-Euler sub-steps."""
+        return ufl.declare_state(self, name, init, alpha=alpha, beta=beta, inf=inf, tau=tau, rhs=rhs).function
 
     def f_NKCC1(self, K_e, K_e_0, K_min_val: float = 3.0, eps: float = 1e-6, cap: float = 1.0):
         """NKCC1 silencing factor.  The reference tests a *symbolic* conditional with a Python

@@ -429,6 +429,8 @@ class RunOutput:
         for nm in ("n", "m", "h"):
             if hasattr(p, nm):
                 data[nm] = getattr(p, nm).numpy()[:nvo]
+        for st in getattr(p, "state_variables", []):
+            data[st.name] = st.function.numpy()[:nvo]
         np.savez(os.path.join(self.prefix, "checkpoints", f"step_{i:06d}_rank{p.comm.rank}.npz"), **data)
 
     # ---- KNPEMIx_solver.py:833-866 (same file names)

@@ -292,6 +292,17 @@ class MixedDimensionalProblem(ABC):
             if isinstance(model, HodgkinHuxley):
                 self.gating_variables = True
                 self.print("Gating variables flag set to True.")
+        # states declared with IonicModel.add_state: advanced by one kernel after the gating update of the built-in model
+        self.state_variables, self.state_rush_larsen, self.state_substeps = fem.collect_states(self.ionic_models)
+        if self.state_variables:
+            for st in self.state_variables:      # n, m, h of the built-in model are checkpoint keys too
+                if st.name in ("n", "m", "h") and getattr(self, st.name, st.function) is not st.function:
+                    raise ValueError(f"state '{st.name}': the built-in Hodgkin-Huxley model owns that name")
+            if self.find_initial_conditions:
+                raise NotImplementedError("steady-state initial conditions do not know the declared states "
+                                          + ", ".join(f"'{st.name}'" for st in self.state_variables)
+                                          + ": provide 'initial_conditions' in the input file")
+            self.gating_variables = True
         ionic_tags = sorted(ionic_tags)
         gamma_tags = sorted(flatten_list([self.gamma_tags]))
         if ionic_tags != gamma_tags and not self.MMS_test and len(ionic_tags) != 0:
@@ -747,7 +758,7 @@ class ProblemKNPEMI(MixedDimensionalProblem):
             roles[id(ui_p[j])] = ("KI", j)
             roles[id(ue_p[j])] = ("KE", j)
         roles[id(self.phi_m_prev)] = ("PHIM", 0)
-        self.aux_functions = []
+        self.aux_functions = [st.function for st in getattr(self, "state_variables", [])]     # states first: fixed slots
         # Tissue configs carry hundreds of membrane tags with the same mechanism list: tags whose compiled program is
         # identical (same bytecode, same constant objects) share one program id.
         # Constants somebody holds a handle to (attributes of the problem, of a mechanism, entries of the ion table) may
@@ -773,12 +784,16 @@ class ProblemKNPEMI(MixedDimensionalProblem):
                 seen[key] = len(self.programs)
                 self.programs[seen[key]] = spec
             self.tag_program[k] = by_terms[tkey] = seen[key]
+        for st in getattr(self, "state_variables", []):
+            fem.compile_state_program(st, roles, self.aux_functions)
         if self.backend is not None and getattr(self.backend, "tag_program", None) != self.tag_program:
             raise RuntimeError("setup_variational_form() changed the membrane-tag -> program map after the backend was created")
         self.a = "hard-wired in knp_kernels.hip (k_assemble_pairs, k_gamma_facets, k_gamma_pairs)"
         self.L = "hard-wired in knp_kernels.hip (k_rhs, k_gamma_facets) + membrane programs"
         if self.backend is not None:
             self.backend.upload_programs()
+            if getattr(self, "state_variables", None):
+                self.backend.state_setup()
 
     def setup_preconditioner(self, use_block_jacobi: bool):
         self.print("Setting up preconditioner ...")

@@ -492,6 +492,8 @@ class SolverKNPEMI:
                 if isinstance(model, HodgkinHuxley):
                     model.update_t_mod()
                     model.update_gating_variables()
+            if getattr(p, "state_variables", None):
+                be.state_update()
         be.timer_mark()
         self._b_is_final = i > 1          # step 1: the null-space projection still modifies b after the assembly
         self.assemble()

@@ -62,6 +62,7 @@ void knp_jit_build(knp_ctx* ctx);
 void knp_jit_release(knp_ctx* ctx);
 void knp_diag_free(knp_ctx* ctx);
 void knp_emi_free(knp_ctx* ctx);
+void knp_state_free(knp_ctx* ctx);
 
 // ---- the EMI model (knp_emi.inc): one unknown per node on the graph knp_create built ------------------------------------------
 struct KnpEmi {
@@ -77,6 +78,22 @@ struct KnpEmi {
     double* d_fvec = nullptr;        // [dim * n_g] membrane integral of every facet against each of its vertices' hat functions
     int aux_need = -1;               // highest aux field + 1 that a membrane program reads; -1: the program table is not built yet
     double* d_st = nullptr;          // [4] CG scalars on the device: r.z of the previous / current iteration (ping-pong), breakdown flag
+};
+
+// ---- membrane state variables (knp_states.inc): one bytecode program per state, all of them run by k_state_update ----------------
+struct KnpStateProg {
+    bool set = false;
+    int kind = 0;                    // 0 gate (OUT 0 = alpha, OUT 1 = beta), 1 general (OUT 0 = dy/dt)
+    int aux_index = -1;              // the aux slot under which the programs read this state
+    int n_regs = 0;
+    bool uses_k = false;             // reads a concentration (KNP_OP_KI / KNP_OP_KE)
+    std::vector<int32_t> code;       // [n_instr*4]
+    std::vector<double> consts;      // travel as kernel arguments of the next knp_state_update
+};
+struct KnpStates {
+    std::vector<KnpStateProg> progs; // one per slot (knp_state_reset sizes it)
+    int32_t* d_code = nullptr;       // the programs' code, one after the other in slot order
+    bool dirty = true;               // d_code is behind progs
 };
 
 // ---- tag map of a diagnostic reduction (knp_diagnostics.inc): items sorted by dense tag index --------------------------------
@@ -405,6 +422,7 @@ struct knp_ctx {
     double diag_consts[KNP_DIAG_MAX_CONSTS] = {};   // host copy: passed to the kernel by value at every launch
     bool diag_prog = false;
     KnpEmi emi;
+    KnpStates states;
     // profiling
     int prof_on = 0;
     std::vector<hipEvent_t> prof_pool;   // recycled timing events

@@ -3015,6 +3015,7 @@ int knp_destroy(knp_ctx* ctx) {
     dev_free(ctx->d_defl_mode); dev_free(ctx->d_defl_einv); dev_free(ctx->d_bc_dofs);
     knp_diag_free(ctx);
     knp_emi_free(ctx);
+    knp_state_free(ctx);
     delete ctx;
     return KNP_OK;
 }
@@ -5018,3 +5019,6 @@ int knp_amg_get_level_info(const knp_ctx* ctx, int32_t hier, int32_t level, int3
 
 // the EMI model: scalar matrix on the node graph, membrane right-hand side, preconditioned conjugate gradients (knp_emi_*)
 #include "knp_emi.inc"
+
+// membrane state variables: one bytecode program per state, one kernel that steps them all (knp_state_*)
+#include "knp_states.inc"
