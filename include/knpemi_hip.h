@@ -41,6 +41,9 @@
  *   knp_diag_set_phim_facets / knp_diag_membrane_potential
  *        integral, minimum and maximum of phi_m per membrane tag: what utils/plot_membrane_potentials.py:48-128 reads per cell from
  *        the reference's per-step checkpoints
+ *   knp_sample_plan_create / knp_sample
+ *        scifem.evaluate_function at many points: the slices the reference cuts out of its checkpoints with pyvista
+ *        (utils/plot_slices.py, plot_slice_membrane.py, plot_slices_geometries.py)
  *   knp_emi_*                        the EMI model (src/CGx/EMI): assemble_matrix_block / assemble_vector_block of the forms
  *                                    EMIx_problem.py:152-157, 215-217 and ksp.solve with KSPCG (EMIx_solver.py)
  *   knp_set_comm                     the MPI calls hidden in PETSc/DOLFINx (ghost updates
@@ -445,6 +448,34 @@ int knp_diag_membrane_fluxes(knp_ctx* ctx, const knp_fields* fields, const doubl
 int knp_diag_set_phim_facets(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr /* host [n_tags+1] */,
                              const int32_t* facets /* host [seg_ptr[n_tags]] */);
 int knp_diag_membrane_potential(knp_ctx* ctx, const knp_fields* fields, double* out /* device [n_tags*3] */);
+/* Field sampling: P1 evaluation of nodal fields at arbitrary points (grids, slices), located on the device once per point set.
+ * Rule: cell T contains p iff all dim+1 barycentric weights of p in T are >= -1e-9; among the containing cells the lowest local cell
+ *   index wins; the stored weights are clipped to [0, 1] and renormalised to sum 1.  Only owned cells are searched, and with side 0 / 1
+ *   only the intracellular / extracellular ones (-1: any).  This is the rule of cgx_hip/output.py::_barycentric.
+ * knp_sample_plan_create: the caller sorts the points into a uniform lattice of bins: bin index along axis k =
+ *   min(max(floor((p_k - bin_origin[k]) / bin_size[k]), 0), bin_shape[k] - 1), bins numbered row-major (last axis fastest),
+ *   bin_pts[bin_ptr[b] .. bin_ptr[b+1]-1] the points of bin b.  One cell-major kernel tests every cell against the points of the bins its
+ *   bounding box overlaps (32-bit integer atomicMin of the cell index per hit: the same bits on every run), one point-major kernel
+ *   stores vertices, weights and side per point.  Work: cells + points + tests inside overlapping bins.  Synchronous; the plan keeps
+ *   12 (dim+1) + 5 bytes of device memory per point.  *plan receives an id >= 0 that belongs to the context.
+ * knp_sample_plan_get: the winning cell (-1: none) and the weights of every point, in the caller's order.
+ * knp_sample: out[f*n_points + pt] = sum_a w_a F[f][v_a] in the order a = 0 .. dim, F[f] = f_i[f] where the winning cell is
+ *   intracellular, f_e[f] where it is extracellular; `fill` where the point is in no cell.  Enqueued on the library's stream, no
+ *   host copy, no synchronisation.  f_i / f_e (or an entry) may be null when no located point of the plan needs that side.
+ * knp_sample_plan_destroy: frees the plan (waits for the stream first); knp_destroy frees the plans that are left.
+ * Errors, all KNP_E_ARG with nothing launched: n_points <= 0, a null array, side outside -1 .. 1, a lattice whose shape does not
+ *   multiply to n_bins or whose sizes are not positive, bin_ptr not running from 0 to n_points or decreasing, bin_pts not a permutation,
+ *   a point that is not finite or not in the bin its coordinates give, an unknown plan, n_fields <= 0, a null field that a located point
+ *   needs. */
+int knp_sample_plan_create(knp_ctx* ctx, int32_t n_points, const double* pts /* host [n_points*dim], metres */,
+                           int32_t side /* -1 any cell, 0 intracellular only, 1 extracellular only */, int32_t n_bins,
+                           const int32_t* bin_ptr /* host [n_bins+1] */, const int32_t* bin_pts /* host [n_points] */,
+                           const double* bin_origin, const double* bin_size, const int32_t* bin_shape /* host [dim] each */,
+                           int32_t* plan /* host */);
+int knp_sample_plan_get(knp_ctx* ctx, int32_t plan, int32_t* cell /* host [n_points] */, double* w /* host [n_points*(dim+1)] */);
+int knp_sample(knp_ctx* ctx, int32_t plan, int32_t n_fields, const double* const* f_i, const double* const* f_e /* host [n_fields]
+               device pointers, [n_vertices] doubles each */, double fill, double* out /* device [n_fields*n_points] */);
+int knp_sample_plan_destroy(knp_ctx* ctx, int32_t plan);
 
 /* ---- the EMI model: two potentials with constant conductivities, ONE unknown per node (reference src/CGx/EMI) ----
  * Unknown n is node n of knp_get_layout; every vector is a device array of n_nodes_owned doubles.  One GPU only: every call

@@ -186,6 +186,60 @@ def parse_membrane_potential_keys(out_cfg, gamma_tags):
     raise ValueError("save_membrane_potentials must be true or a list of membrane tags")
 
 
+def parse_sample_grids(out_cfg, dim, factor, save_interval, n_steps):
+    """``sample_grids`` / ``sample_interval`` of ``solver.output``: (entries, interval).  Each entry: ``name``, ``origin`` and ``axes``
+    in metres (the config gives mesh units, like point_evaluation), ``shape``, ``fields``, ``records``.  Absent or empty: ([], interval)
+    and nothing is allocated or launched.  Every invalid entry raises a ValueError that names it."""
+    from .sampling import MAX_GRID_BYTES, MERGED_FIELDS
+    grids = out_cfg.get("sample_grids") or []
+    interval = int(out_cfg.get("sample_interval", save_interval))
+    if interval < 1:
+        raise ValueError("sample_interval must be at least 1")
+    if not isinstance(grids, (list, tuple)):
+        raise ValueError("sample_grids must be a list of entries")
+    entries, seen = [], set()
+    for k, g in enumerate(grids):
+        what = f"sample_grids[{k}]"
+        if not isinstance(g, dict) or "name" not in g:
+            raise ValueError(f"{what}: an entry is a mapping with a name, origin, axes and shape")
+        name = str(g["name"])
+        what += f" ('{name}')"
+        if name in seen:
+            raise ValueError(f"{what}: the name is used twice")
+        seen.add(name)
+        for key in ("origin", "axes", "shape"):
+            if key not in g:
+                raise ValueError(f"{what}: missing key '{key}'")
+        try:
+            origin = np.asarray(g["origin"], dtype=np.float64).ravel()
+            axes = np.atleast_2d(np.asarray(g["axes"], dtype=np.float64))
+            shape = [int(s) for s in np.atleast_1d(g["shape"])]
+        except (TypeError, ValueError) as e:
+            raise ValueError(f"{what}: origin, axes and shape must be numbers ({e})") from None
+        if origin.shape[0] < dim or axes.ndim != 2 or axes.shape[1] < dim:
+            raise ValueError(f"{what}: origin and axes need {dim} components")
+        if len(axes) != len(shape):
+            raise ValueError(f"{what}: {len(axes)} axes but {len(shape)} entries in shape")
+        if not 1 <= len(axes) <= 3:
+            raise ValueError(f"{what}: one to three axes")
+        if min(shape) < 2:
+            raise ValueError(f"{what}: at least two points per axis (shape {shape})")
+        if not np.all(np.abs(axes[:, :dim]).sum(axis=1) > 0):
+            raise ValueError(f"{what}: an axis is the zero vector")
+        fields = list(g.get("fields", MERGED_FIELDS))
+        bad = [f for f in fields if f not in MERGED_FIELDS]
+        if bad or not fields or len(set(fields)) != len(fields):
+            raise ValueError(f"{what}: unknown, repeated or no field name(s) {bad or fields}: choose from {list(MERGED_FIELDS)}")
+        records = n_steps // interval + 1
+        nbytes = 8 * records * len(fields) * int(np.prod(shape))
+        if nbytes > MAX_GRID_BYTES:
+            raise ValueError(f"{what}: {records} records of {len(fields)} fields on {shape} points take {nbytes} bytes, more than the "
+                             f"{MAX_GRID_BYTES} allowed for one grid: raise sample_interval (now {interval}) or coarsen the grid")
+        entries.append({"name": name, "origin": origin[:dim] * factor, "axes": axes[:, :dim] * factor, "shape": tuple(shape),
+                        "fields": fields, "records": records})
+    return entries, interval
+
+
 class RunOutput:
     """Everything ``SolverKNPEMI`` records besides the solve itself; one instance per solver."""
 
@@ -252,6 +306,16 @@ class RunOutput:
             self.probe_idx = torch.as_tensor(self.probes["vertex"][self.probe_cols], dtype=torch.int64, device=be.device)
             self.probe_fields = [p.phi_m_prev] + ([p.n, p.m, p.h] if hasattr(p, "n") else [])
             self.probe_rows = torch.zeros((len(self.probe_fields), n_rec, len(self.probe_cols)), dtype=torch.float64, device=be.device)
+        # fields on grids and slices (output key sample_grids): per entry one located GridSampler and one preallocated device tensor
+        # [records, fields, *shape]; a record is one gather launch, the tensors are read once in save_sample_grids()
+        self.grids = []
+        for g in getattr(solver, "sample_grids", None) or []:
+            from .sampling import GridSampler, merged_functions
+            os.makedirs(self.prefix, exist_ok=True)
+            gs = GridSampler(p, g["origin"], g["axes"], g["shape"])
+            _, f_i, f_e = merged_functions(p, g["fields"])
+            buf = torch.zeros((g["records"], len(f_i)) + gs.shape, dtype=torch.float64, device=solver.backend.device)
+            self.grids.append({"name": g["name"], "sampler": gs, "f_i": f_i, "f_e": f_e, "buf": buf, "t": []})
         self.xdmf = None
         if getattr(solver, "save_xdmfs", False):
             os.makedirs(self.prefix, exist_ok=True)
@@ -297,6 +361,10 @@ class RunOutput:
             if len(self.probe_cols):
                 for k, fn in enumerate(self.probe_fields):
                     torch.index_select(fn.x.array, 0, self.probe_idx, out=self.probe_rows[k, r])
+        if self.grids and (i % s.sample_interval == 0):
+            for g in self.grids:
+                g["sampler"](g["f_i"], g["f_e"], out=g["buf"][i // s.sample_interval])
+                g["t"].append(float(p.t.value))
         if s.save_cpoints and (i % s.save_interval == 0):
             self.checkpoint(i)
         if self.xdmf is not None and i > 0 and (i % s.save_interval == 0):       # reference :471
@@ -504,6 +572,19 @@ class RunOutput:
         np.save(out + "phi_m_points_xyz.npy", self.probes["xyz"])
         if len(self.probe_fields) == 4:
             np.save(out + "gating_points.npy", np.ascontiguousarray(np.transpose(pts[1:], (1, 2, 0))))
+
+    def save_sample_grids(self):
+        """Per ``sample_grids`` entry: grid_<name>.npy [records, fields, *shape] (the merged fields: the _i function inside intracellular
+        cells, the _e function inside extracellular ones, NaN outside the mesh) at steps 0, sample_interval, 2 sample_interval, ...;
+        grid_<name>_tags.npy int32 [*shape], the cell tag per point, -1 outside; grid_<name>_xyz.npy [*shape, dim] in metres;
+        grid_<name>_t.npy the recorded times [s].  One read-back per grid."""
+        out = self.p.output_dir
+        for g in self.grids:
+            gs = g["sampler"]
+            np.save(out + f"grid_{g['name']}.npy", g["buf"][:len(g["t"])].cpu().numpy())
+            np.save(out + f"grid_{g['name']}_tags.npy", np.ascontiguousarray(gs.cell_tag, dtype=np.int32))
+            np.save(out + f"grid_{g['name']}_xyz.npy", gs.xyz)
+            np.save(out + f"grid_{g['name']}_t.npy", np.array(g["t"]))
 
     def figures(self):
         """PNG plots of the traces (KNPEMIx_solver.py:645-764) when matplotlib is installed; the data are exported either way."""

@@ -855,6 +855,22 @@ class ProblemKNPEMI(MixedDimensionalProblem):
         return {"tag": np.array(tags, dtype=np.int64), "area": area, "mean": val[:, 0].copy(), "min": val[:, 1].copy(),
                 "max": val[:, 2].copy()}
 
+    def sample(self, points_or_sampler, fields=None):
+        """The merged fields ``Na``, ``K``, ``Cl``, ``phi`` (or the subset ``fields``, in that order) at points: the ``_i`` function where
+        the point lies in an intracellular cell, the ``_e`` function where it lies in an extracellular one, NaN where no cell contains
+        it.  ``points_or_sampler``: points [n, dim] in metres (located on the device for this call) or a ``FieldSampler`` /
+        ``GridSampler`` of cgx_hip/sampling.py to reuse its location.  Returns NumPy [n_fields, n] ([n_fields, *shape] from a grid).
+        One gather launch (knp_sample) and one read-back."""
+        from .sampling import FieldSampler, merged_functions
+        _, f_i, f_e = merged_functions(self, fields)
+        own = not isinstance(points_or_sampler, FieldSampler)
+        sampler = FieldSampler(self, points_or_sampler) if own else points_or_sampler
+        try:
+            return sampler(f_i, f_e).cpu().numpy()
+        finally:
+            if own:
+                sampler.close()
+
     def print_conservation(self):
         """Total ion amounts and, per intracellular tag, volume, membrane area and charge: the reference's lines
         (KNPEMIx_problem.py:807-843), printed on rank 0 from ``ion_budget()``."""

@@ -80,6 +80,10 @@ class SolverKNPEMI:
     # vertex per tag every membrane_potential_interval steps (phi_m_tags.npy, phi_m_points.npy); None: off
     membrane_potential_tags = None
     membrane_potential_interval = 1
+    # output keys sample_grids (a list of named point lattices) / sample_interval (default: save_interval): the merged fields on each
+    # lattice every sample_interval steps (grid_<name>.npy and its _tags, _xyz, _t files); empty: off
+    sample_grids = ()
+    sample_interval = 20
     tot_its = 0.0
     tot_assembly_time = 0.0
     tot_solver_time = 0.0
@@ -120,6 +124,9 @@ class SolverKNPEMI:
         self.membrane_potential_tags, self.membrane_potential_interval = parse_membrane_potential_keys(out, problem.gamma_tags)
         if "save_interval" in out:
             self.save_interval = out["save_interval"]
+        from .output import parse_sample_grids
+        self.sample_grids, self.sample_interval = parse_sample_grids(out, problem.local_mesh.coords.shape[1], float(problem.mesh_conversion_factor),
+                                                                     int(self.save_interval), int(self.time_steps))
         self.out_file_prefix = problem.output_dir
         self.direct_solver = bool(solver_config["direct"])
         self.view_input = solver_config.get("view_ksp", False)
@@ -398,7 +405,7 @@ class SolverKNPEMI:
         from .output import RunOutput
         self.output = RunOutput(self) if (self.save_pngs or self.save_dat or self.save_cpoints or self.save_xdmfs or p.point_evaluation
                                           or self.save_ion_budget or self.save_fluxes
-                                          or self.membrane_potential_tags is not None) else None
+                                          or self.membrane_potential_tags is not None or self.sample_grids) else None
         if self.output is not None:
             self.output.record(0)
 
@@ -559,6 +566,8 @@ class SolverKNPEMI:
             self.output.save_fluxes()
         if self.membrane_potential_tags is not None and self.output is not None:
             self.output.save_membrane_potentials()
+        if self.sample_grids and self.output is not None:
+            self.output.save_sample_grids()
         if self.save_pngs and self.output is not None:
             self.output.figures()
         if self.save_dat:

@@ -63,6 +63,7 @@ void knp_jit_release(knp_ctx* ctx);
 void knp_diag_free(knp_ctx* ctx);
 void knp_emi_free(knp_ctx* ctx);
 void knp_state_free(knp_ctx* ctx);
+void knp_sample_free(knp_ctx* ctx);
 
 // ---- the EMI model (knp_emi.inc): one unknown per node on the graph knp_create built ------------------------------------------
 struct KnpEmi {
@@ -106,6 +107,19 @@ struct KnpDiagMap {
     double* d_partial = nullptr;   // [(n_tags + n_chunks) * values] per (chunk, tag) partial sums
     int32_t* d_long = nullptr;     // [n_long] the tags of the workgroup combine
     int n_long = 0;
+};
+
+// ---- sampling plan (knp_sample.inc): the located points of one knp_sample_plan_create, in bin order on the device -----------------
+struct KnpSamplePlan {
+    bool live = false;
+    int n = 0;
+    int n_side[2] = {0, 0};        // located points whose winning cell is intracellular / extracellular
+    int32_t* d_perm = nullptr;     // [n] the caller's index of the point in internal position i
+    int32_t* d_vert = nullptr;     // [(dim+1)][n] vertices of the winning cell (0 where there is none)
+    double* d_w = nullptr;         // [(dim+1)][n] clipped, renormalised weights (0 where there is no cell)
+    uint8_t* d_side = nullptr;     // [n] 0 / 1 side of the winning cell, 2: no cell
+    std::vector<int32_t> h_cell;   // [n] winning cell or -1, caller's order
+    std::vector<double> h_w;       // [n*(dim+1)] weights, caller's order
 };
 
 // ---- device-side program ------------------------------------------------------------------
@@ -423,6 +437,7 @@ struct knp_ctx {
     bool diag_prog = false;
     KnpEmi emi;
     KnpStates states;
+    std::vector<KnpSamplePlan> sample_plans;   // knp_sample_plan_create: the id is the index; a destroyed slot is reused
     // profiling
     int prof_on = 0;
     std::vector<hipEvent_t> prof_pool;   // recycled timing events

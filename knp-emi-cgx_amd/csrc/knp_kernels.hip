@@ -3016,6 +3016,7 @@ int knp_destroy(knp_ctx* ctx) {
     knp_diag_free(ctx);
     knp_emi_free(ctx);
     knp_state_free(ctx);
+    knp_sample_free(ctx);
     delete ctx;
     return KNP_OK;
 }
@@ -5016,6 +5017,9 @@ int knp_amg_get_level_info(const knp_ctx* ctx, int32_t hier, int32_t level, int3
 
 // per-tag diagnostics: ion amounts per cell tag, membrane integrals of one program (knp_diag_*)
 #include "knp_diagnostics.inc"
+
+// field sampling at arbitrary points: point locator, interpolation weights, one gather per record (knp_sample_*)
+#include "knp_sample.inc"
 
 // the EMI model: scalar matrix on the node graph, membrane right-hand side, preconditioned conjugate gradients (knp_emi_*)
 #include "knp_emi.inc"
