@@ -334,7 +334,9 @@ int knp_gmres_prepare(knp_ctx* ctx, const double* b);
  * on one GPU n_dof_local == n_dof_owned and nothing is written.
  * On one GPU without hooks, Dirichlet rows or deflation the first iteration of every cycle is enqueued before the host reads the
  * cycle's initial residual norm (one wait per cycle start less; same kernels, order and results; KNP_GMRES_AHEAD=0, read at
- * knp_pc_setup, restores the in-order form).  KNP_ST_READBACK and KNP_ST_ALLREDUCE count what ran, a discarded iteration included. */
+ * knp_pc_setup, restores the in-order form).  KNP_ST_READBACK and KNP_ST_ALLREDUCE count what ran, a discarded iteration included.
+ * The kernel that builds v_{j+1} returns at once on an iteration whose residual estimate already meets the tolerance (nobody reads
+ * that vector; the host takes its decisions from the same values as before; KNP_UPDATE_EARLY=0, read at knp_pc_setup: off). */
 int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, double atol, int32_t max_it,
                     int32_t restart, int32_t* its, double* rnorm, int32_t* reason);
 /* Flexible GMRES(restart): what the reference gets from PETSc with ksp_type fgmres, or gmres with norm_type unpreconditioned
@@ -361,6 +363,25 @@ int knp_fgmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doub
 /* ---- state transfer ---- */
 int knp_pack(knp_ctx* ctx, const knp_fields_out* fields, double* x);
 int knp_unpack(knp_ctx* ctx, const double* x, const knp_fields_out* fields);
+/* Fused tail of a solve (optional; without these two calls every launch is as before).
+ * knp_set_unpack_target: where knp_unpack will put the solution (all nine pointers set; NULL clears the registration).  With a
+ * target registered, knp_gmres_solve ends in ONE kernel that adds the last correction to x, unpacks x into the target (exactly what
+ * knp_unpack writes) and keeps the node-indexed concentration copy the next matrix assembly reads -- when the update belongs to the
+ * cycle after which the solve returns and has at most 8 columns, on one GPU without hooks, peer-to-peer plans, deflation, Dirichlet
+ * rows or kernel-class timing beyond the SpMV's (KNP_FUSED_TAIL=0, read at knp_pc_setup: never).  x is bit for bit what the
+ * separate kernels give.  knp_unpack(ctx, x, fields) of that x into that target then returns at once.  The library forgets that the
+ * target is current at every entry that writes x or the fields (any later solve, knp_project_nullspace, knp_pack,
+ * knp_set_dirichlet, knp_pc_setup, knp_assemble_precond, this call); it cannot see the CALLER write x or the target between the solve
+ * and knp_unpack: register again (or clear) after doing so.
+ * knp_fields_unchanged: the caller's promise that nobody has written the concentration fields of the target since the last
+ * knp_unpack.  One shot: the next knp_assemble_matrix(_async) -- given the same six concentration pointers -- then skips its
+ * node-indexed copy pass if the solve's tail has already written it, and the promise is consumed either way.
+ * KNP_ST_FUSED_TAILS / KNP_ST_KNOD_SKIPS count both. */
+int knp_set_unpack_target(knp_ctx* ctx, const knp_fields_out* fields /* or NULL */);
+int knp_fields_unchanged(knp_ctx* ctx);
+/* test hook: the node-indexed concentration copy {k0, k1, k2, 0} per local node, host [4 * n_nodes] (synchronises; KNP_E_STATE on
+ * contexts whose assembly reads per-cell means instead) */
+int knp_get_nodal_conc(knp_ctx* ctx, double* out);
 int knp_hh_update(knp_ctx* ctx, const double* phi_m, double* n, double* m, double* h, int32_t count,
                   double dt, double phi_rest, int32_t rush_larsen, int32_t substeps);
 /* Membrane state variables: nodal fields that a mechanism declares and the library advances after every solve.  Every state is one
@@ -544,7 +565,10 @@ enum { KNP_ST_BNORM = 0 /* ||B b|| of the last solve */, KNP_ST_ALLREDUCE = 1 /*
        KNP_ST_BLOCKED = 6 /* bit h set: the fused cycle of hierarchy h runs on node-blocked operators */,
        KNP_ST_FUSED_LEVELS = 7 /* levels >= 1 that run in fused form inside the level-by-level cycle, all hierarchies */,
        KNP_ST_FUSED_DOTS = 8 /* reductions whose first stage ran in the preconditioner's last leg (KNP_FUSED_DOTS) */,
-       KNP_ST_SPMV_DOTS = 9 /* reductions whose first stage ran in the SpMV on A (knp_fgmres_solve, KNP_SPMV_DOTS) */, KNP_ST_COUNT = 10 };
+       KNP_ST_SPMV_DOTS = 9 /* reductions whose first stage ran in the SpMV on A (knp_fgmres_solve, KNP_SPMV_DOTS) */,
+       KNP_ST_FUSED_TAILS = 10 /* solves whose last update also unpacked x (knp_set_unpack_target, KNP_FUSED_TAIL) */,
+       KNP_ST_KNOD_SKIPS = 11 /* matrix assemblies that skipped the node-indexed concentration copy (knp_fields_unchanged) */,
+       KNP_ST_COUNT = 12 };
 int knp_get_stats(const knp_ctx* ctx, double* out /* host [KNP_ST_COUNT] */);
 /* bytes the kernels of one application must move, from the sizes of the arrays they read and write (per-class roofline): [0] SpMV on A,
  * [1] one preconditioner application, [2] matrix assembly of one step, [3] right-hand side assembly, [4] one owned vector */

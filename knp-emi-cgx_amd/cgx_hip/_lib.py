@@ -118,6 +118,9 @@ SIGNATURES = {
     "knp_fgmres_solve": (C.c_int, [vp, vp, vp, C.c_double, C.c_double, C.c_int32, C.c_int32, i32p, f64p, i32p]),
     "knp_pack": (C.c_int, [vp, C.POINTER(FieldsOut), vp]),
     "knp_unpack": (C.c_int, [vp, vp, C.POINTER(FieldsOut)]),
+    "knp_set_unpack_target": (C.c_int, [vp, C.POINTER(FieldsOut)]),
+    "knp_fields_unchanged": (C.c_int, [vp]),
+    "knp_get_nodal_conc": (C.c_int, [vp, f64p]),
     "knp_hh_update": (C.c_int, [vp, vp, vp, vp, vp, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32]),
     "knp_state_reset": (C.c_int, [vp, C.c_int32]),
     "knp_state_set_program": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_int32, C.c_int32, i32p, C.c_int32, f64p]),

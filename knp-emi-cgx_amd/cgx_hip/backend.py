@@ -465,16 +465,38 @@ class Backend(StateUpdate):
         f.phi_e = p.wh[1][3].data_ptr()
         f.phi_m = p.phi_m_prev.data_ptr()
         self._fields_out_cache = f
+        # where the solve's last kernel may unpack x itself (knp_set_unpack_target; also forgets whatever the library held as current)
+        self.check(self.lib.knp_set_unpack_target(self.ctx, C.byref(f)))
         return f
+
+    # ---- what the library cannot see: torch writing the tensors behind the concentration fields between two of its calls -----
+    def _field_marks(self):
+        """(data_ptr, _version) of the six concentration tensors and of phi_m_prev: an in-place torch operation raises the
+        version, a rebinding changes the pointer; the library's own kernels change neither"""
+        p = self.p
+        wi, we = p.wh[0], p.wh[1]
+        ts = (wi[0].x.array, wi[1].x.array, wi[2].x.array, we[0].x.array, we[1].x.array, we[2].x.array, p.phi_m_prev.x.array)
+        return [(t.data_ptr(), t._version) for t in ts]
+
+    def _promise_fields_unchanged(self):
+        """Before a matrix assembly: tell the library that torch has not written the fields since the last unpack (one shot: the
+        assembly may then skip its node-indexed copy of the concentrations when the solve's tail has written it).  One walk over
+        the tensors per step: the marks are compared with those of the PREVIOUS assembly, a window that contains the one asked for."""
+        marks = self._field_marks()
+        if getattr(self, "_unpacked", False) and marks == getattr(self, "_asm_marks", None):
+            self.check(self.lib.knp_fields_unchanged(self.ctx))
+        self._asm_marks, self._unpacked = marks, False
 
     # ------------------------------------------------------------------ operations
     def assemble_matrix(self):
         f = self.fields()
+        self._promise_fields_unchanged()
         self.check(self.lib.knp_assemble_matrix(self.ctx, C.byref(f)))
 
     def assemble_matrix_async(self):
         """matrix assembly on the library's own stream (next to the right-hand side chain of the same step); joined by the solve"""
         f = self.fields()
+        self._promise_fields_unchanged()
         self.check(self.lib.knp_assemble_matrix_async(self.ctx, C.byref(f)))
 
     def assemble_rhs(self):
@@ -495,6 +517,7 @@ class Backend(StateUpdate):
     def unpack(self):
         f = self.fields_out()
         self.check(self.lib.knp_unpack(self.ctx, C.c_void_p(self.x.data_ptr()), C.byref(f)))
+        self._unpacked = True
 
     def hh_update(self, phi_m, n, m, h, dt, phi_rest, rush_larsen, substeps):
         self.check(self.lib.knp_hh_update(self.ctx, C.c_void_p(phi_m.data_ptr()), C.c_void_p(n.data_ptr()),
@@ -754,11 +777,17 @@ class Backend(StateUpdate):
 
     def stats(self):
         """||B b|| of the last solve and the exchange / read-back counters since the last ``profile_reset``."""
-        out = (C.c_double * 10)()   # KNP_ST_COUNT
+        out = (C.c_double * 12)()   # KNP_ST_COUNT
         self.check(self.lib.knp_get_stats(self.ctx, out))
         return {"bnorm": out[0], "allreduces": int(out[1]), "halos": int(out[2]), "readbacks": int(out[3]), "fused": int(out[4]),
                 "norm_fallbacks": int(out[5]), "blocked": int(out[6]), "fused_levels": int(out[7]),
-                "fused_dots": int(out[8]), "spmv_dots": int(out[9])}
+                "fused_dots": int(out[8]), "spmv_dots": int(out[9]), "fused_tails": int(out[10]), "knod_skips": int(out[11])}
+
+    def nodal_conc(self):
+        """the library's node-indexed copy of the concentrations, [n_nodes, 4] on the host (test hook, synchronises)"""
+        out = np.empty((self.n_nodes, 4), dtype=np.float64)
+        self.check(self.lib.knp_get_nodal_conc(self.ctx, _f64(out)))
+        return out
 
     def traffic_model(self):
         """bytes one application of each kernel class must move (knp_get_traffic_model)"""

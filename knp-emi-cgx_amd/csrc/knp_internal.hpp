@@ -421,6 +421,25 @@ struct knp_ctx {
     int64_t n_allreduce = 0, n_halo = 0, n_readback = 0;
     int64_t n_fused_dots = 0;   // reductions whose first stage ran in the cycle's last leg (KNP_FUSED_DOTS)
     int64_t n_spmv_dots = 0;    // reductions whose first stage ran in the SpMV on A (KNP_SPMV_DOTS, flexible GMRES)
+    // Fused tail of a solve (k_lincomb_unpack: the last x += V y of knp_gmres_solve also unpacks x into the registered fields and
+    // writes the node-indexed concentrations d_knod).  `tail_ok`: every unknown is reached through node_i / node_e exactly once and
+    // there are no ghost nodes (knp_create).  `fields_current`: the registered fields equal unpack(tail_x); `knod_current`: d_knod
+    // holds the concentrations of tail_x.  Both are CLEARED by every entry that writes x or could make the fields or d_knod stale:
+    //   knp_gmres_solve, knp_fgmres_solve (krylov_begin), knp_project_nullspace, knp_pack, knp_set_unpack_target, knp_set_dirichlet,
+    //   knp_pc_setup, knp_assemble_precond (rewrites d_knod from its own fields), a knp_unpack that runs k_unpack, and the matrix
+    //   assembly itself (knod_current and the caller's promise are consumed there).
+    // `fields_promise`: knp_fields_unchanged -- the caller vouches that nobody wrote the concentration fields since the last
+    // knp_unpack; one shot, consumed by the next matrix assembly.
+    int fused_tail = 1;       // KNP_FUSED_TAIL=0: off (read at knp_pc_setup)
+    int update_early = 1;     // k_update_scale returns early on the converging iteration (KNP_UPDATE_EARLY=0: off, read at knp_pc_setup)
+    bool tail_ok = false;
+    bool have_tail_target = false;
+    knp_fields_out tail_target = {};
+    const double* tail_x = nullptr;
+    bool fields_current = false, knod_current = false, fields_promise = false;
+    bool knod_skipped = false;       // the last matrix assembly skipped k_nodal_conc (knp_get_traffic_model)
+    int64_t n_fused_tail = 0;        // solves that ended in k_lincomb_unpack
+    int64_t n_knod_skip = 0;         // matrix assemblies that skipped k_nodal_conc
     // step timers (knp_timer_mark / knp_timer_read): timing events recorded on the main stream, read back in one go
     std::vector<hipEvent_t> tm_events;
     size_t tm_used = 0;

@@ -450,8 +450,17 @@ k_assemble_nodes_tr(int n_nodes, DevParams P, int cmax, const int32_t* __restric
 }
 
 // what the volume assembly reads the previous concentrations from: the node-indexed copy (fused cell means) or the per-cell means
-static void launch_cell_means(knp_ctx* ctx, const FieldPtrs& f) {
+// `matrix`: the matrix assembly, which may find d_knod already written by the tail of the last solve (k_lincomb_unpack) -- skipped
+// iff the caller promised that the fields were not written since (knp_fields_unchanged) AND knod_current AND these are the
+// concentration fields the tail unpacked into.  Promise and knod_current are consumed here whatever the outcome.
+static void launch_cell_means(knp_ctx* ctx, const FieldPtrs& f, bool matrix = false) {
     const KnpHostGraph& g = ctx->g;
+    bool skip = matrix && ctx->asm_dmax > 0 && ctx->fields_promise && ctx->knod_current && ctx->have_tail_target && (ctx->prof_on & ~1) == 0;
+    for (int j = 0; j < 3 && skip; ++j) skip = f.ki[j] == ctx->tail_target.k_i[j] && f.ke[j] == ctx->tail_target.k_e[j];
+    ctx->fields_promise = false;
+    ctx->knod_current = false;
+    if (matrix) ctx->knod_skipped = skip;
+    if (skip) { ++ctx->n_knod_skip; return; }
     if (ctx->asm_dmax > 0)
         hipLaunchKernelGGL(k_nodal_conc, dim3(nblocks(g.n_nodes)), dim3(NT), 0, ctx->stream, g.n_nodes, ctx->d_node_vertex, ctx->d_node_side, f, ctx->d_knod);
     else
@@ -2033,10 +2042,13 @@ __global__ void k_gm_init(GmLayout L, double* __restrict__ gm, const double* __r
 // Pythagoras (or, explicit_slot >= 0, the explicitly reduced one), previous Givens rotations, the new rotation, the residual
 // estimate |g_{j+1}|; published to pinned host memory together with the sequence word the host spins on.
 // v_{j+1} = (w - sum_i h[i] V_i - gauge part) / ||.||  in one pass (state: {||w'||^2, flag}); with flag != 0 the vector is left
-// unnormalised (the explicit-norm fallback normalises it afterwards)
+// unnormalised (the explicit-norm fallback normalises it afterwards).  `ttol` > 0: the solve stops at a residual estimate (st[2], what
+// the host reads from the mirror) <= ttol with the flag clear, and then nobody reads v_{j+1}: every block returns before it touches
+// w or V.  0: never (the flexible driver, an iteration enqueued before ||B b|| is known, KNP_UPDATE_EARLY=0).
 __global__ void __launch_bounds__(NT)
 k_update_scale(int n, int64_t ldv, int m, const double* __restrict__ V, const double* __restrict__ h, const double* __restrict__ w,
-               const double* __restrict__ st, double ns_scale, double* __restrict__ out) {
+               const double* __restrict__ st, double ns_scale, double* __restrict__ out, double ttol) {
+    if (ttol > 0.0 && st[1] == 0.0 && st[2] <= ttol) return;
     const double inv = st[1] == 0.0 ? 1.0 / sqrt(st[0]) : 1.0;
     const double mean = ns_scale != 0.0 ? h[m] * ns_scale : 0.0;
     const int n2 = n >> 1;
@@ -2490,6 +2502,7 @@ struct OutPtrs {
     double* ke[3];
     double *phi_i, *phi_e, *phi_m;
 };
+static int out_ptrs(knp_ctx* ctx, const knp_fields_out* f, OutPtrs& o, bool need_phim);
 __global__ void __launch_bounds__(NT)
 k_pack(int n_nodes, const int32_t* __restrict__ node_vertex, const uint8_t* __restrict__ node_side, OutPtrs f,
        double* __restrict__ x) {
@@ -2517,6 +2530,64 @@ k_unpack(int n_v, const int32_t* __restrict__ node_i, const int32_t* __restrict_
     f.phi_i[v] = pi;
     f.phi_e[v] = pe;
     f.phi_m[v] = pi - pe;
+}
+// k_lincomb_solve for the cycle that ends a solve, one thread per VERTEX: x += V y at the four unknowns of the vertex's intracellular
+// and extracellular node (the same operations in the same order per unknown: x is bit for bit k_lincomb_solve's), then what
+// k_unpack writes for the vertex and the node's record of k_nodal_conc ({k0, k1, k2, 0}; knod may be null).  Every node belongs to
+// exactly one vertex (checked at knp_create), so every unknown is written once.
+__global__ void __launch_bounds__(NT)
+k_lincomb_unpack(GmLayout L, int jd, double* __restrict__ gm, int n_v, int64_t ldv, const double* __restrict__ V, double* __restrict__ x,
+                 const int32_t* __restrict__ node_i, const int32_t* __restrict__ node_e, OutPtrs f, double* __restrict__ knod) {
+    __shared__ double sH[8 * 8], sg[8], sy[8];
+    if (threadIdx.x < jd * jd) sH[threadIdx.x] = gm[L.H(threadIdx.x % jd, threadIdx.x / jd)];   // sH[i + jd*k] = H(i, k)
+    if (threadIdx.x < jd) sg[threadIdx.x] = gm[L.g() + threadIdx.x];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int i = jd - 1; i >= 0; --i) {
+            double s = sg[i];
+            for (int k = i + 1; k < jd; ++k) s -= sH[i + jd * k] * sy[k];
+            sy[i] = s / sH[i + jd * i];
+        }
+        if (blockIdx.x == 0)
+            for (int i = 0; i < jd; ++i) gm[L.y() + i] = sy[i];
+    }
+    __syncthreads();
+    const int v = blockIdx.x * NT + threadIdx.x;
+    if (v >= n_v) return;
+    double u[2][4];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        const int nd = s ? node_e[v] : node_i[v];
+        u[s][0] = u[s][1] = u[s][2] = u[s][3] = 0.0;
+        if (nd < 0) continue;
+        const size_t e = (size_t)4 * nd;
+        const double2 a = *reinterpret_cast<const double2*>(x + e), b = *reinterpret_cast<const double2*>(x + e + 2);
+        double x0 = a.x, x1 = a.y, x2 = b.x, x3 = b.y;
+        for (int i = 0; i < jd; ++i) {
+            const double* __restrict__ vi = V + (int64_t)i * ldv + e;
+            const double2 p = *reinterpret_cast<const double2*>(vi), q = *reinterpret_cast<const double2*>(vi + 2);
+            const double yi = sy[i];
+            x0 += yi * p.x;
+            x1 += yi * p.y;
+            x2 += yi * q.x;
+            x3 += yi * q.y;
+        }
+        *reinterpret_cast<double2*>(x + e) = make_double2(x0, x1);
+        *reinterpret_cast<double2*>(x + e + 2) = make_double2(x2, x3);
+        if (knod) {
+            *reinterpret_cast<double2*>(knod + e) = make_double2(x0, x1);
+            *reinterpret_cast<double2*>(knod + e + 2) = make_double2(x2, 0.0);
+        }
+        u[s][0] = x0; u[s][1] = x1; u[s][2] = x2; u[s][3] = x3;
+    }
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        f.ki[j][v] = u[0][j];
+        f.ke[j][v] = u[1][j];
+    }
+    f.phi_i[v] = u[0][3];
+    f.phi_e[v] = u[1][3];
+    f.phi_m[v] = u[0][3] - u[1][3];
 }
 
 // partial[blk] = max |v| over the block's share
@@ -2968,6 +3039,19 @@ int knp_create(knp_ctx** out, const knp_mesh_desc* mesh) {
         KCHK(dev_upload(ctx, &ctx->d_nodes_int, li));
         KCHK(dev_upload(ctx, &ctx->d_nodes_bnd, lb));
     }
+    {   // fused tail (k_lincomb_unpack): no ghost nodes, and node_i / node_e reach every node exactly once, from its own vertex and side
+        int64_t hits = 0;
+        bool ok = g.n_nodes == g.n_nodes_owned && ctx->n_dof_owned == 4 * g.n_nodes && ctx->n_dof_local == ctx->n_dof_owned &&
+                  (int)g.node_i.size() == g.n_v && (int)g.node_e.size() == g.n_v;
+        for (int v = 0; ok && v < g.n_v; ++v)
+            for (int s = 0; s < 2; ++s) {
+                const int nd = s ? g.node_e[v] : g.node_i[v];
+                if (nd < 0) continue;
+                if (nd >= g.n_nodes || g.node_vertex[nd] != v || g.node_side[nd] != s) { ok = false; break; }
+                ++hits;
+            }
+        ctx->tail_ok = ok && hits == g.n_nodes;   // (vertex and side identify the node, so `hits` distinct nodes were reached)
+    }
     // free the big host arrays that are no longer needed (pattern kept for export)
     std::vector<int32_t>().swap(g.contrib_cell);
     std::vector<double>().swap(g.contrib_k);
@@ -3253,6 +3337,7 @@ int knp_set_dirichlet(knp_ctx* ctx, int32_t n, const int32_t* dofs) {
         ctx->n_bc = n;
     }
     ctx->asm_dt = -1.0;   // constant blocks of the touched rows must be rewritten if the set changes
+    ctx->fields_current = ctx->knod_current = false;
     return KNP_OK;
 }
 
@@ -3302,7 +3387,7 @@ static int assemble_matrix_on_stream(knp_ctx* ctx, const knp_fields* fields, boo
     const DevParams P = make_params(ctx);
     FieldPtrs f = make_fields(fields);
     ProfScope ps(ctx, 3);
-    launch_cell_means(ctx, f);
+    launch_cell_means(ctx, f, true);
     // The (k,k) and (phi,k) blocks do not depend on the previous solution (SURVEY 3.2 obs. 1): after the first
     // assembly only the K[k_prev]-type and membrane entries are rewritten, unless KNP_ASM_FULL=1 asks for the
     // reference's behaviour (A.zeroEntries() + full re-assembly, KNPEMIx_solver.py:110-115).
@@ -3644,6 +3729,7 @@ int knp_project_nullspace(knp_ctx* ctx, double* v) {
     CHECK_CTX(ctx);
     side_discard(ctx);
     if (!v) return KNP_E_ARG;
+    ctx->fields_current = ctx->knod_current = false;   // v may be the x the last solve unpacked
     return project_ns(ctx, v);
 }
 
@@ -4555,6 +4641,9 @@ int knp_pc_setup(knp_ctx* ctx, int32_t kind) {
     ctx->fused_dots = !(getenv("KNP_FUSED_DOTS") && atoi(getenv("KNP_FUSED_DOTS")) == 0);   // read at every knp_pc_setup, like KNP_FUSED
     ctx->spmv_dots = !(getenv("KNP_SPMV_DOTS") && atoi(getenv("KNP_SPMV_DOTS")) == 0);
     ctx->gmres_ahead = !(getenv("KNP_GMRES_AHEAD") && atoi(getenv("KNP_GMRES_AHEAD")) == 0);
+    ctx->fused_tail = !(getenv("KNP_FUSED_TAIL") && atoi(getenv("KNP_FUSED_TAIL")) == 0);
+    ctx->update_early = !(getenv("KNP_UPDATE_EARLY") && atoi(getenv("KNP_UPDATE_EARLY")) == 0);
+    ctx->fields_current = ctx->knod_current = false;
     for (int h = 0; h < KNP_MAX_HIER; ++h) ctx->hier[h].fused = 0;
     if (kind == KNP_PC_AMG) ctx->hier[0].fused = fused_eligible(ctx, ctx->hier[0]) ? 1 : 0;
     if (kind == KNP_PC_AMG_BT || kind == KNP_PC_AMG_LT) {   // both or none: the potential hierarchy then works on compact vectors
@@ -4770,11 +4859,44 @@ static int out_ptrs(knp_ctx* ctx, const knp_fields_out* f, OutPtrs& o, bool need
     o.phi_i = f->phi_i; o.phi_e = f->phi_e; o.phi_m = f->phi_m;
     return KNP_OK;
 }
+static bool same_target(const knp_ctx* ctx, const knp_fields_out* f) {
+    if (!ctx->have_tail_target) return false;
+    const knp_fields_out& t = ctx->tail_target;
+    for (int j = 0; j < 3; ++j)
+        if (f->k_i[j] != t.k_i[j] || f->k_e[j] != t.k_e[j]) return false;
+    return f->phi_i == t.phi_i && f->phi_e == t.phi_e && f->phi_m == t.phi_m;
+}
+int knp_set_unpack_target(knp_ctx* ctx, const knp_fields_out* f) {
+    CHECK_CTX(ctx);
+    ctx->fields_current = ctx->knod_current = ctx->fields_promise = false;
+    ctx->have_tail_target = false;
+    if (!f) return KNP_OK;
+    OutPtrs o;
+    KCHK(out_ptrs(ctx, f, o, true));
+    ctx->tail_target = *f;
+    ctx->have_tail_target = true;
+    return KNP_OK;
+}
+int knp_fields_unchanged(knp_ctx* ctx) {
+    CHECK_CTX(ctx);
+    ctx->fields_promise = true;
+    return KNP_OK;
+}
+int knp_get_nodal_conc(knp_ctx* ctx, double* out) {
+    CHECK_CTX(ctx);
+    if (!out) return KNP_E_ARG;
+    if (ctx->asm_dmax <= 0 || !ctx->d_knod) { ctx->err = "this context's assembly keeps no node-indexed concentration copy"; return KNP_E_STATE; }
+    KCHK(join_asm(ctx));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    HIPCHK(hipMemcpy(out, ctx->d_knod, (size_t)4 * ctx->g.n_nodes * sizeof(double), hipMemcpyDeviceToHost));
+    return KNP_OK;
+}
 int knp_pack(knp_ctx* ctx, const knp_fields_out* f, double* x) {
     CHECK_CTX(ctx);
     if (!x) return KNP_E_ARG;
     OutPtrs o;
     KCHK(out_ptrs(ctx, f, o, false));
+    ctx->fields_current = ctx->knod_current = false;
     hipLaunchKernelGGL(k_pack, dim3(nblocks(ctx->g.n_nodes)), dim3(NT), 0, ctx->stream, ctx->g.n_nodes, ctx->d_node_vertex,
                        ctx->d_node_side, o, x);
     HIPCHK(hipGetLastError());
@@ -4785,6 +4907,8 @@ int knp_unpack(knp_ctx* ctx, const double* x, const knp_fields_out* f) {
     if (!x) return KNP_E_ARG;
     OutPtrs o;
     KCHK(out_ptrs(ctx, f, o, true));
+    if (ctx->fields_current && x == ctx->tail_x && same_target(ctx, f)) return KNP_OK;   // the solve's tail has written exactly this
+    ctx->fields_current = ctx->knod_current = false;
     KCHK(join_asm(ctx));   // the fields written here are what an assembly still in flight reads
     KCHK(halo_update(ctx, const_cast<double*>(x)));
     hipLaunchKernelGGL(k_unpack, dim3(nblocks(ctx->g.n_v)), dim3(NT), 0, ctx->stream, ctx->g.n_v, ctx->d_node_i, ctx->d_node_e, x, o);
@@ -4876,6 +5000,7 @@ int knp_profile_reset(knp_ctx* ctx) {
     ctx->n_allreduce = ctx->n_halo = ctx->n_readback = ctx->n_norm_fallback = 0;
     ctx->n_fused_dots = 0;
     ctx->n_spmv_dots = 0;
+    ctx->n_fused_tail = ctx->n_knod_skip = 0;
     return KNP_OK;
 }
 // Bytes the kernels of one application must move, from the sizes of the arrays they read and write (the "algorithmic bytes" of the
@@ -4931,7 +5056,8 @@ int knp_get_traffic_model(const knp_ctx* ctx, double* out) {
     // a_t written (32 B per pair); + the membrane entries (facet matrices read, a_t slots updated, a_x written)
     // the previous concentrations: node-indexed copy + one 32-byte record per neighbour + the byte table of the cells' vertices
     // (fused cell means), or the per-cell pass (connectivity, 3 (d+1) gathers, a 32-byte record written) + a record read per cell of a node
-    const double conc = ctx->asm_dmax > 0 ? (double)g.n_nodes * 56.0 + np_ * 36.0 + (double)ctx->n_node_cells * g.nv1
+    // (the node-indexed copy pass -- 56 B per node -- only when the last matrix assembly ran it: the solve's tail may have written the copy)
+    const double conc = ctx->asm_dmax > 0 ? (ctx->knod_skipped ? 0.0 : (double)g.n_nodes * 56.0) + np_ * 36.0 + (double)ctx->n_node_cells * g.nv1
                                           : (double)g.n_c * (4.0 * g.nv1 + 32.0 + 24.0 * g.nv1) + (double)ctx->n_node_cells * 36.0;
     out[2] = (double)(ctx->n_tc > 0 ? ctx->n_tc : ctx->n_contrib) * 9.0 + conc + np_ * 32.0 + ngp * (64.0 + 48.0);
     out[3] = no * (8.0 * 4.0 + 9.0) + np_ * (8.0 + 4.0 + 24.0) + (double)g.n_g * g.dim * 7.0 * 8.0 * 2.0;
@@ -4954,6 +5080,8 @@ int knp_get_stats(const knp_ctx* ctx, double* out) {
     out[KNP_ST_FUSED_LEVELS] = (double)nlf;
     out[KNP_ST_FUSED_DOTS] = (double)ctx->n_fused_dots;
     out[KNP_ST_SPMV_DOTS] = (double)ctx->n_spmv_dots;
+    out[KNP_ST_FUSED_TAILS] = (double)ctx->n_fused_tail;
+    out[KNP_ST_KNOD_SKIPS] = (double)ctx->n_knod_skip;
     return KNP_OK;
 }
 int knp_get_launch_info(const knp_ctx* ctx, int32_t* out, int n) {

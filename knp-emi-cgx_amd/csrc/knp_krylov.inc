@@ -263,6 +263,7 @@ static int krylov_begin(knp_ctx* ctx, const double* b, double* x, int32_t max_it
         ctx->err = "restart must be in [1," + std::to_string(GM_MAX_RESTART) + "] and max_it >= 0";
         return KNP_E_ARG;
     }
+    ctx->fields_current = ctx->knod_current = false;   // x is about to change
     KCHK(ensure_work(ctx, restart));
     if (flexible && ctx->pc_kind != KNP_PC_NONE) KCHK(ensure_z(ctx, restart));   // with no preconditioner Z is V: nothing is allocated or copied
     prof_collect_ready(ctx);
@@ -309,7 +310,10 @@ static int gm_read_state(const KrylovSolve& K, double* res, int* flag) {
 // Two halves: arnoldi_step_enqueue launches the reduction, the Givens step and v_{j+1} and waits for nothing;
 // arnoldi_step_read waits for the residual estimate and flag (`have`: the caller has read them already, they are in *res, *flag)
 // and runs the cancellation fallback.  arnoldi_step_finish is both, back to back.
-static int arnoldi_step_enqueue(const KrylovSolve& K, int j, const double* w, double* vn, int first_nb, int first_stride) {
+// `early` > 0: the stop threshold of the solve, with which k_update_scale skips v_{j+1} on the converging iteration (nothing reads
+// that vector after a converged stop: arnoldi_step_read touches vn only under the cancellation flag, which excludes the early
+// return, and the update of x uses V_0..V_j); 0: the vector is always built.
+static int arnoldi_step_enqueue(const KrylovSolve& K, int j, const double* w, double* vn, int first_nb, int first_stride, double early = 0.0) {
     knp_ctx* ctx = K.ctx;
     hipStream_t st = ctx->stream;
     const GmLayout GL = K.GL;
@@ -340,7 +344,7 @@ static int arnoldi_step_enqueue(const KrylovSolve& K, int j, const double* w, do
         hipLaunchKernelGGL(k_givens, dim3(1), dim3(64), 0, st, GL, j, nsi, K.inv_cnt, ctx->d_red, -1, gm,
                            ctx->mirror() ? ctx->h_red_dev + GM_RES : nullptr, ctx->mirror() ? ctx->h_seq_dev : nullptr, ++ctx->seq_counter);
     }
-    hipLaunchKernelGGL(k_update_scale, dim3(nb), dim3(NT), 0, st, n, ldv, j + 1, ctx->d_V, ctx->d_red, w, gm + GL.st(), K.inv_cnt, vn);
+    hipLaunchKernelGGL(k_update_scale, dim3(nb), dim3(NT), 0, st, n, ldv, j + 1, ctx->d_V, ctx->d_red, w, gm + GL.st(), K.inv_cnt, vn, early);
     HIPCHK(hipGetLastError());
     return KNP_OK;
 }
@@ -464,7 +468,7 @@ int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doubl
             hipLaunchKernelGGL(k_gm_init, dim3(1), dim3(64), 0, st, GL, gm, ctx->d_red + 60);
         }
     };
-    auto enqueue_iteration = [&](int j) -> int {
+    auto enqueue_iteration = [&](int j, double early) -> int {
         double* vj = ctx->d_V + (size_t)j * ldv;
         double* vn = ctx->d_V + (size_t)(j + 1) * ldv;
         KCHK(spmv_A(ctx, vj, nullptr, ctx->d_t, false));
@@ -475,7 +479,7 @@ int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doubl
         // k_multi_dot (arnoldi_step_enqueue).
         DotReq dq{j + 1, ns, ldv, ctx->d_V, ctx->d_partial};
         KCHK(pc_apply_proj(ctx, ctx->d_t, ctx->d_w, ns ? 0 : cnt, (ctx->fused_dots && fin_ok(ctx) && j + 1 <= BU_MAX_M) ? &dq : nullptr));
-        return arnoldi_step_enqueue(K, j, ctx->d_w, vn, dq.done ? dq.nb : 0, RED_WIDE);
+        return arnoldi_step_enqueue(K, j, ctx->d_w, vn, dq.done ? dq.nb : 0, RED_WIDE, early);
     };
     // Enqueue-ahead form of a cycle start: nothing on the device depends on the host's reading of ||B r||, so v_0 and iteration 0 are
     // launched behind the norm's reduction and the host waits ONCE, for iteration 0's k_reduce_fin (stream order: the norm's has
@@ -484,6 +488,10 @@ int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doubl
     // there every reduction publishes to the pinned mirror and the sequence word, through k_reduce_fin or (KNP_FIN=0) k_proj_norm / k_givens.
     const bool ahead_ok = ctx->gmres_ahead && ctx->mirror() && ctx->h_seq && ctx->h_seq_dev && !ctx->halo && !ctx->allreduce && !ctx->p2p &&
                           !ctx->level_comm && ctx->defl_m == 0 && ctx->n_bc == 0 && max_it > 0 && (ctx->prof_on & ~1) == 0;
+    // The update after which the solve returns may also unpack x (k_lincomb_unpack): one GPU, nothing between the update and the
+    // caller (krylov_end's halo is a no-op there), every unknown reached from a vertex, a registered target, no class timing.
+    const bool tail_ok = ctx->fused_tail && ctx->tail_ok && ctx->have_tail_target && !ctx->halo && !ctx->allreduce && !ctx->level_comm && !ctx->p2p &&
+                         ctx->defl_m == 0 && ctx->n_bc == 0 && (ctx->prof_on & ~1) == 0;
     while (true) {
         // r = M (b - A x)
         KCHK(spmv_A(ctx, x, b, ctx->d_t, true));
@@ -513,7 +521,8 @@ int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doubl
         };
         if (ahead) {
             enqueue_v0(true);
-            KCHK(enqueue_iteration(0));
+            // (||B b|| still on the side stream: the threshold is not known yet, v_1 is built unconditionally)
+            KCHK(enqueue_iteration(0, (ctx->update_early && !lazy_bnorm) ? K.ttol : 0.0));
             KCHK(gm_read_state(K, &res_a, &flag_a));   // the one wait; slots 60, 61 of the mirror are the norm's
             if (ctx->h_red[61] != 0.0) KCHK(redo_residual());   // cancellation in the residual norm: pc_norm_read projects explicitly
         } else {
@@ -551,13 +560,24 @@ int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doubl
             const bool have = ahead && j == 0;   // iteration 0 ran ahead: its residual estimate and flag were read at the wait above
             int flag = have ? flag_a : 0;
             if (have) res = res_a;
-            else KCHK(enqueue_iteration(j));
+            else KCHK(enqueue_iteration(j, ctx->update_early ? K.ttol : 0.0));
             KCHK(arnoldi_step_read(K, j, ctx->d_V + (size_t)(j + 1) * ldv, &res, &flag, have));
             if (krylov_stop_test(K, j, flag, res, max_it, &it, &jd, reason)) { stop = true; break; }
         }
         if (jd > 0) {
             ProfScope ps(ctx, 1);
-            krylov_update_plain(K, jd, ctx->d_V, x);
+            if (stop && tail_ok && jd <= 8) {
+                OutPtrs o;
+                KCHK(out_ptrs(ctx, &ctx->tail_target, o, true));
+                hipLaunchKernelGGL(k_lincomb_unpack, dim3(nblocks(ctx->g.n_v)), dim3(NT), 0, st, GL, jd, gm, ctx->g.n_v, ldv, ctx->d_V, x, ctx->d_node_i,
+                                   ctx->d_node_e, o, ctx->asm_dmax > 0 ? ctx->d_knod : nullptr);
+                ctx->tail_x = x;
+                ctx->fields_current = true;
+                ctx->knod_current = ctx->asm_dmax > 0;
+                ++ctx->n_fused_tail;
+            } else {
+                krylov_update_plain(K, jd, ctx->d_V, x);
+            }
         }
         if (stop) break;
     }
