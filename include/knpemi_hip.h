@@ -44,6 +44,9 @@
  *   knp_sample_plan_create / knp_sample
  *        scifem.evaluate_function at many points: the slices the reference cuts out of its checkpoints with pyvista
  *        (utils/plot_slices.py, plot_slice_membrane.py, plot_slices_geometries.py)
+ *   knp_functional_create / knp_functional_eval
+ *        dfx.fem.assemble_scalar(dfx.fem.form(<UFL expression> * dx(tag))) for any expression of the nodal fields, their gradients
+ *        and the coordinates: the norms of main.py:70-84 and tests/KNPEMI/electric_potential_norms_*.py, print_conservation, ...
  *   knp_emi_*                        the EMI model (src/CGx/EMI): assemble_matrix_block / assemble_vector_block of the forms
  *                                    EMIx_problem.py:152-157, 215-217 and ksp.solve with KSPCG (EMIx_solver.py)
  *   knp_set_comm                     the MPI calls hidden in PETSc/DOLFINx (ghost updates
@@ -80,6 +83,7 @@ extern "C" {
 #define KNP_STATE_MAX_INSTR 768  /* instructions of all state programs together (knp_state_set_program) */
 #define KNP_STATE_MAX_CONSTS 128 /* constants of all state programs together */
 #define KNP_MAX_AMG_LEVELS 16
+#define KNP_FUNCTIONAL_MAX_Q 125 /* quadrature points per cell of a volume functional (knp_functional_create) */
 
 #define KNP_OK 0
 #define KNP_E_ARG (-1)
@@ -497,6 +501,37 @@ int knp_sample_plan_get(knp_ctx* ctx, int32_t plan, int32_t* cell /* host [n_poi
 int knp_sample(knp_ctx* ctx, int32_t plan, int32_t n_fields, const double* const* f_i, const double* const* f_e /* host [n_fields]
                device pointers, [n_vertices] doubles each */, double fill, double* out /* device [n_fields*n_points] */);
 int knp_sample_plan_destroy(knp_ctx* ctx, int32_t plan);
+/* Volume functionals: per-tag integrals over cells of one bytecode program (the opcodes of knp_set_program) evaluated at the points
+ * of a simplex quadrature rule.  A functional is a plan that belongs to the context, like a sampling plan; several may be live.
+ * knp_functional_create: a tag map of owned cells like knp_diag_set_cell_tags (cells of either side, each at most once), the rule
+ *   (q_bary: dim+1 barycentric coordinates per point in the order of the cell's vertices; q_w sums to 1), the program with at most
+ *   KNP_DIAG_MAX_CONSTS constants, and per aux slot what it holds: aux_deriv[k] == -1 the field fields->aux[k] itself, a in 0 .. dim-1
+ *   its derivative d/dx_a.  Synchronous.  *id receives an id >= 0.
+ * knp_functional_set_constants: replaces the constants on the host; they travel as kernel arguments of the next evaluation (no
+ *   copy, no synchronisation).
+ * knp_functional_eval: out[t*n_out + j] = sum over the cells T of tag t of |T| sum_q q_w[q] OUT_j(program at point q of T).  There
+ *   KNP_OP_KI a / KNP_OP_KE a / KNP_OP_PHIM read the P1 interpolant of fields->k_i[a] / k_e[a] / phi_m at T's vertices, KNP_OP_X a
+ *   the point's coordinate, KNP_OP_AUX k the interpolant of fields->aux[k] or, where aux_deriv[k] == a, the derivative
+ *   sum_b grad(lambda_b)_a (f(v_b) - f(v_0)) of that field on T (constant per cell; the gradients come from the cell's coordinates
+ *   inside the kernel, and the differences are taken first, so a field's constant offset does not cost digits).  Only the pointers of slots the code reads are used: the others may be null.  One cell per lane, 128 cells per block,
+ *   the interpreter's register file in LDS (1 KiB per register the program uses, at most 48 KiB); partials are combined in a fixed
+ *   order (one wave per tag of at most 64 chunks of 128 cells, one workgroup per longer tag): the same bits on every run.
+ *   Enqueued on the library's stream; never waits for the device.
+ * knp_functional_destroy: frees the plan (waits for the stream first); knp_destroy frees the plans that are left.
+ * Errors leave nothing launched and no plan: KNP_E_ARG for a null argument, n_q outside 1 .. KNP_FUNCTIONAL_MAX_Q, n_out outside
+ *   1 .. 3, n_aux outside 0 .. KNP_MAX_AUX, an aux_deriv outside -1 .. dim-1, an invalid or empty program, one that reads an aux slot
+ *   >= n_aux or writes an output >= n_out, more than KNP_DIAG_MAX_CONSTS constants or another count in set_constants, an unknown id,
+ *   a cell that is not owned or listed twice, a seg_ptr that does not start at 0 or decreases, in eval a null pointer of a slot the
+ *   code reads; KNP_E_MESH when a derivative is bound and a listed cell is flat (zero determinant, or gradients that are not
+ *   finite; checked on the host at create).  n_tags == 0 is a successful no-op. */
+int knp_functional_create(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr /* host [n_tags+1] */,
+                          const int32_t* cells /* host [seg_ptr[n_tags]] */, int32_t n_q, const double* q_bary /* host [n_q*(dim+1)] */,
+                          const double* q_w /* host [n_q] */, int32_t n_instr, const int32_t* code /* host [n_instr*4] */,
+                          int32_t n_consts, const double* consts /* host */, int32_t n_aux, const int32_t* aux_deriv /* host [n_aux] */,
+                          int32_t n_out /* 1..3 */, int32_t* id /* host */);
+int knp_functional_set_constants(knp_ctx* ctx, int32_t id, int32_t n_consts, const double* consts /* host */);
+int knp_functional_eval(knp_ctx* ctx, int32_t id, const knp_fields* fields, double* out /* device [n_tags*n_out] */);
+int knp_functional_destroy(knp_ctx* ctx, int32_t id);
 
 /* ---- the EMI model: two potentials with constant conductivities, ONE unknown per node (reference src/CGx/EMI) ----
  * Unknown n is node n of knp_get_layout; every vector is a device array of n_nodes_owned doubles.  One GPU only: every call

@@ -15,6 +15,7 @@ KNP_MAX_IONS = 3
 KNP_MAX_AUX = 8
 KNP_MAX_PROG_REGS = 48
 KNP_DIAG_MAX_CONSTS = 64
+KNP_FUNCTIONAL_MAX_Q = 125
 KNP_STATE_MAX_INSTR = 768
 KNP_STATE_MAX_CONSTS = 128
 KNP_SZ_COUNT = 16
@@ -141,6 +142,11 @@ SIGNATURES = {
     "knp_sample_plan_get": (C.c_int, [vp, C.c_int32, i32p, f64p]),
     "knp_sample": (C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(vp), C.POINTER(vp), C.c_double, vp]),
     "knp_sample_plan_destroy": (C.c_int, [vp, C.c_int32]),
+    "knp_functional_create": (C.c_int, [vp, C.c_int32, i32p, i32p, C.c_int32, f64p, f64p, C.c_int32, i32p, C.c_int32, f64p, C.c_int32, i32p,
+                                        C.c_int32, i32p]),
+    "knp_functional_set_constants": (C.c_int, [vp, C.c_int32, C.c_int32, f64p]),
+    "knp_functional_eval": (C.c_int, [vp, C.c_int32, C.POINTER(Fields), vp]),
+    "knp_functional_destroy": (C.c_int, [vp, C.c_int32]),
     "knp_emi_setup": (C.c_int, [vp, C.c_double, C.c_double, C.c_double, C.c_double]),
     "knp_emi_get_csr": (C.c_int, [vp, i32p, i32p, f64p]),
     "knp_emi_set_dirichlet": (C.c_int, [vp, C.c_int32, i32p]),

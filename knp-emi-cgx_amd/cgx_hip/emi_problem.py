@@ -396,6 +396,12 @@ class ProblemEMI(MixedDimensionalProblem):
         self.aux_functions = aux
         return self.programs
 
+    def assemble_scalar(self, integrand_i=None, integrand_e=None, tags=None, degree=2):
+        """``ProblemKNPEMI.assemble_scalar`` for the EMI model: every Function (phi_i, phi_e, phi_M, gates, states, the user's own)
+        is an aux field of the functional.  Needs the library context, i.e. ``setup_bilinear_form()`` first."""
+        from .functionals import assemble_scalar
+        return assemble_scalar(self, integrand_i, integrand_e, tags, degree)
+
     def setup_preconditioner(self):
         """The preconditioner matrix is the EMI matrix itself (with the Dirichlet elimination).  The reference's P = sigma K + M per side
         (EMIx_problem.py:225-248) is nearly singular per side in SI units and is not built."""

@@ -136,6 +136,16 @@ class Op(Expr):
         self.op, self.args, self.imm = op, tuple(args), imm
 
 
+class Derivative(Expr):
+    """d/dx_axis of a P1 ``Function``: constant on every cell.  Only the integrands of volume functionals may hold one
+    (cgx_hip/functionals.py); membrane and state programs are evaluated at vertices and facets, where it has no single value."""
+
+    def __init__(self, function, axis):
+        if not isinstance(function, Function):
+            raise TypeError("grad() takes a Function (a P1 nodal field)")
+        self.function, self.axis = function, int(axis)
+
+
 def as_expr(v):
     if isinstance(v, Expr):
         return v
@@ -164,6 +174,26 @@ def conditional(c, t, f): return Op("SEL", (as_expr(c), as_expr(t), as_expr(f)))
 def SpatialCoordinate(mesh): return [Coordinate(d) for d in range(mesh.geometry.dim)]
 
 
+def grad(f):
+    """``ufl.grad`` of a P1 Function: the list of its ``dim`` partial derivatives"""
+    if not isinstance(f, Function):
+        raise TypeError("grad() takes a Function (a P1 nodal field)")
+    return [Derivative(f, a) for a in range(f.function_space.mesh.geometry.dim)]
+
+
+def inner(a, b):
+    """``ufl.inner`` of two scalars, or of two lists of equally many components (``grad``)"""
+    va, vb = isinstance(a, (list, tuple)), isinstance(b, (list, tuple))
+    if va != vb or (va and (len(a) != len(b) or not len(a))):
+        raise ValueError("inner() takes two scalars or two lists of the same length")
+    if not va:
+        return as_expr(a) * as_expr(b)
+    total = as_expr(a[0]) * as_expr(b[0])
+    for x, y in zip(a[1:], b[1:]):
+        total = total + as_expr(x) * as_expr(y)
+    return total
+
+
 max = max_value      # noqa: A001  (the reference spells it ufl.max / ufl.min)
 min = min_value      # noqa: A001
 
@@ -185,20 +215,41 @@ class ProgramSpec:
     """Compiled membrane program: ``code`` int32[n,4], constant table and the Python objects
     behind the table (so that time-dependent Constants can be refreshed every step)."""
 
-    def __init__(self, code, const_sources, aux_functions):
+    def __init__(self, code, const_sources, aux_functions, aux_derivs=None):
         self.code = code
         self.const_sources = const_sources      # list of Constant | float
         self.aux_functions = aux_functions      # list of Function, index = aux slot
+        self.aux_derivs = aux_derivs            # None, or per aux slot -1 (the Function's value) | axis (its derivative)
 
     def constants(self):
         return np.array([float(c.value) if isinstance(c, Constant) else float(c) for c in self.const_sources],
                         dtype=np.float64)
 
 
-def compile_program(outputs, field_roles, aux_functions=None):
+class AuxSlotsExhausted(ValueError):
+    """the expressions of one program read more than KNP_MAX_AUX nodal fields (and derivatives) that need an aux slot"""
+
+
+def compile_program(outputs, field_roles, aux_functions=None, aux_derivs=None):
     """outputs: list of 3 expressions (I_ch^k).  field_roles: dict id(Function) -> ('KI', j) |
-    ('KE', j) | ('PHIM', 0).  Other Functions get aux slots (shared list ``aux_functions``)."""
+    ('KE', j) | ('PHIM', 0).  Other Functions get aux slots (shared list ``aux_functions``).
+    ``aux_derivs``: a list that runs parallel to ``aux_functions`` (-1: the slot holds the Function's value, a: its derivative
+    d/dx_a) lets the expressions hold ``Derivative`` nodes: each (Function, axis) pair takes one slot.  Without it a
+    ``Derivative`` is refused, as in every membrane and state program."""
     aux_functions = aux_functions if aux_functions is not None else []
+    if aux_derivs is not None and len(aux_derivs) != len(aux_functions):
+        raise ValueError("aux_derivs must have one entry per aux function")
+
+    def aux_slot(f, axis):
+        for k, g in enumerate(aux_functions):
+            if g is f and (aux_derivs is None or aux_derivs[k] == axis):
+                return k
+        if len(aux_functions) >= KNP_MAX_AUX:
+            raise AuxSlotsExhausted(f"more than {KNP_MAX_AUX} auxiliary nodal fields in membrane expressions")
+        aux_functions.append(f)
+        if aux_derivs is not None:
+            aux_derivs.append(axis)
+        return len(aux_functions) - 1
     nodes = []                # SSA list: (opname, argidx tuple, imm)
     index = {}                # structural key -> ssa id
     consts = []
@@ -234,15 +285,10 @@ def compile_program(outputs, field_roles, aux_functions=None):
         if isinstance(e, Function):
             role = field_roles.get(id(e))
             if role is None:
-                for k, f in enumerate(aux_functions):
-                    if f is e:
-                        role = ("AUX", k)
-                        break
-                else:
-                    if len(aux_functions) >= KNP_MAX_AUX:
-                        raise ValueError(f"more than {KNP_MAX_AUX} auxiliary nodal fields in membrane expressions")
-                    aux_functions.append(e)
-                    role = ("AUX", len(aux_functions) - 1)
+                role = ("AUX", aux_slot(e, -1))
+            return emit(role, (role[0], (), role[1]))
+        if isinstance(e, Derivative) and aux_derivs is not None:
+            role = ("AUX", aux_slot(e.function, e.axis))
             return emit(role, (role[0], (), role[1]))
         if isinstance(e, Op):
             args = tuple(visit(a) for a in e.args)
@@ -292,7 +338,7 @@ def compile_program(outputs, field_roles, aux_functions=None):
             free.append(r)
     for k, oid in enumerate(out_ids):
         code.append((OPS["OUT"], 0, k, reg[oid]))
-    return ProgramSpec(np.array(code, dtype=np.int32).reshape(-1, 4), consts, aux_functions)
+    return ProgramSpec(np.array(code, dtype=np.int32).reshape(-1, 4), consts, aux_functions, aux_derivs)
 
 
 # ------------------------------------------------------------------------------------------
@@ -392,7 +438,8 @@ def compile_state_program(state, field_roles, aux_functions):
 # host evaluation (setup-time scalars such as the stimulus area; never on the timed path)
 # ------------------------------------------------------------------------------------------
 def evaluate_numpy(e, env):
-    """Evaluate an expression with NumPy. env: {'x': [arrays per axis], 'fields': {id(Function): array}}."""
+    """Evaluate an expression with NumPy. env: {'x': [arrays per axis], 'fields': {id(Function): array}} and, for expressions
+    with derivatives, 'grads': {(id(Function), axis): array}."""
     e = as_expr(e)
     if isinstance(e, (Literal,)):
         return e.value
@@ -404,6 +451,8 @@ def evaluate_numpy(e, env):
         return env["x"][e.axis]
     if isinstance(e, Function):
         return env["fields"][id(e)]
+    if isinstance(e, Derivative):
+        return env["grads"][(id(e.function), e.axis)]
     a = [evaluate_numpy(x, env) for x in e.args]
     op = e.op
     if op == "ADD": return a[0] + a[1]

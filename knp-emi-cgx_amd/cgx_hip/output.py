@@ -316,6 +316,13 @@ class RunOutput:
             _, f_i, f_e = merged_functions(p, g["fields"])
             buf = torch.zeros((g["records"], len(f_i)) + gs.shape, dtype=torch.float64, device=solver.backend.device)
             self.grids.append({"name": g["name"], "sampler": gs, "f_i": f_i, "f_e": f_e, "buf": buf, "t": []})
+        # volume functionals (SolverKNPEMI.add_functional): one row of a preallocated device tensor per record, read once in
+        # save_functionals()
+        self.functionals = []
+        for name, F, interval in getattr(solver, "functionals", None) or []:
+            os.makedirs(self.prefix, exist_ok=True)
+            buf = torch.zeros((solver.time_steps // interval + 1, len(F.tags), F.n_out), dtype=torch.float64, device=solver.backend.device)
+            self.functionals.append({"name": name, "F": F, "interval": interval, "buf": buf})
         self.xdmf = None
         if getattr(solver, "save_xdmfs", False):
             os.makedirs(self.prefix, exist_ok=True)
@@ -365,6 +372,9 @@ class RunOutput:
             for g in self.grids:
                 g["sampler"](g["f_i"], g["f_e"], out=g["buf"][i // s.sample_interval])
                 g["t"].append(float(p.t.value))
+        for g in self.functionals:
+            if i % g["interval"] == 0:
+                g["F"](out=g["buf"][i // g["interval"]])
         if s.save_cpoints and (i % s.save_interval == 0):
             self.checkpoint(i)
         if self.xdmf is not None and i > 0 and (i % s.save_interval == 0):       # reference :471
@@ -585,6 +595,15 @@ class RunOutput:
             np.save(out + f"grid_{g['name']}_tags.npy", np.ascontiguousarray(gs.cell_tag, dtype=np.int32))
             np.save(out + f"grid_{g['name']}_xyz.npy", gs.xyz)
             np.save(out + f"grid_{g['name']}_t.npy", np.array(g["t"]))
+
+    def save_functionals(self):
+        """Per ``add_functional`` entry: functional_<name>.npy [records, n_tags, n_out] at steps 0, interval, 2 interval, ...;
+        functional_<name>_tags.npy: per row (tag, side 0 intra / 1 extra, volume).  One read-back per functional."""
+        out = self.p.output_dir
+        for g in self.functionals:
+            F = g["F"]
+            np.save(out + f"functional_{g['name']}.npy", g["buf"].cpu().numpy())
+            np.save(out + f"functional_{g['name']}_tags.npy", np.stack([F.tags, F.side, F.volume], axis=1).astype(np.float64))
 
     def figures(self):
         """PNG plots of the traces (KNPEMIx_solver.py:645-764) when matplotlib is installed; the data are exported either way."""

@@ -871,6 +871,15 @@ class ProblemKNPEMI(MixedDimensionalProblem):
             if own:
                 sampler.close()
 
+    def assemble_scalar(self, integrand_i=None, integrand_e=None, tags=None, degree=2):
+        """``dfx.fem.assemble_scalar(dfx.fem.form(integrand * dx(tags)))``: the integral of ``integrand_i`` over the intracellular
+        cell tags and of ``integrand_e`` over the extracellular ones (``tags``: default every tag of the sides that have an integrand),
+        summed over the tags, with a rule exact to ``degree``.  An integrand is an expression of cgx_hip/fem.py -- Functions,
+        ``fem.grad``, Constants, coordinates -- or a list of up to three: a float for a single expression, else an array.  One
+        launch pair per side (knp_functional_eval) and one read-back; keep a ``functionals.VolumeFunctional`` to integrate again."""
+        from .functionals import assemble_scalar
+        return assemble_scalar(self, integrand_i, integrand_e, tags, degree)
+
     def print_conservation(self):
         """Total ion amounts and, per intracellular tag, volume, membrane area and charge: the reference's lines
         (KNPEMIx_problem.py:807-843), printed on rank 0 from ``ion_budget()``."""

@@ -128,6 +128,7 @@ class SolverKNPEMI:
         self.sample_grids, self.sample_interval = parse_sample_grids(out, problem.local_mesh.coords.shape[1], float(problem.mesh_conversion_factor),
                                                                      int(self.save_interval), int(self.time_steps))
         self.out_file_prefix = problem.output_dir
+        self.functionals = []      # add_functional(): (name, VolumeFunctional, interval)
         self.direct_solver = bool(solver_config["direct"])
         self.view_input = solver_config.get("view_ksp", False)
         norm_set = False
@@ -405,7 +406,7 @@ class SolverKNPEMI:
         from .output import RunOutput
         self.output = RunOutput(self) if (self.save_pngs or self.save_dat or self.save_cpoints or self.save_xdmfs or p.point_evaluation
                                           or self.save_ion_budget or self.save_fluxes
-                                          or self.membrane_potential_tags is not None or self.sample_grids) else None
+                                          or self.membrane_potential_tags is not None or self.sample_grids or self.functionals) else None
         if self.output is not None:
             self.output.record(0)
 
@@ -568,10 +569,28 @@ class SolverKNPEMI:
             self.output.save_membrane_potentials()
         if self.sample_grids and self.output is not None:
             self.output.save_sample_grids()
+        if self.functionals and self.output is not None:
+            self.output.save_functionals()
         if self.save_pngs and self.output is not None:
             self.output.figures()
         if self.save_dat:
             self.export_data()
+
+    def add_functional(self, name, F, interval=1):
+        """Record the ``VolumeFunctional`` ``F`` (cgx_hip/functionals.py) at step 0 and at every ``interval``-th step, on the device and
+        without a host wait; the run ends with functional_<name>.npy [records, n_tags, n_out] and functional_<name>_tags.npy (tag,
+        side, volume per row).  Call it before ``solve()`` / ``prepare()``."""
+        from .functionals import VolumeFunctional
+        if getattr(self, "_prepared", False):
+            raise RuntimeError("add_functional() must be called before solve()")
+        name = str(name)
+        if not name or any(name == n for n, _, _ in self.functionals):
+            raise ValueError(f"a functional needs a name of its own (got '{name}')")
+        if not isinstance(F, VolumeFunctional) or F.problem is not self.problem:
+            raise ValueError("add_functional() takes a VolumeFunctional of this solver's problem")
+        if int(interval) < 1:
+            raise ValueError("interval must be at least 1")
+        self.functionals.append((name, F, int(interval)))
 
     def solve(self):
         self.prepare()

@@ -64,6 +64,7 @@ void knp_diag_free(knp_ctx* ctx);
 void knp_emi_free(knp_ctx* ctx);
 void knp_state_free(knp_ctx* ctx);
 void knp_sample_free(knp_ctx* ctx);
+void knp_functional_free(knp_ctx* ctx);
 
 // ---- the EMI model (knp_emi.inc): one unknown per node on the graph knp_create built ------------------------------------------
 struct KnpEmi {
@@ -120,6 +121,19 @@ struct KnpSamplePlan {
     uint8_t* d_side = nullptr;     // [n] 0 / 1 side of the winning cell, 2: no cell
     std::vector<int32_t> h_cell;   // [n] winning cell or -1, caller's order
     std::vector<double> h_w;       // [n*(dim+1)] weights, caller's order
+};
+
+// ---- volume functional (knp_functional.inc): tag map of cells, quadrature rule and program of one knp_functional_create ---------------
+struct KnpFunctional {
+    bool live = false;
+    int n_q = 0, n_out = 0, n_instr = 0, n_regs = 0, n_consts = 0;
+    unsigned need = 0;             // the field slots the code reads (FN_* bits)
+    int8_t aux_deriv[KNP_MAX_AUX] = {-1, -1, -1, -1, -1, -1, -1, -1};   // per aux slot: -1 value, a = d/dx_a
+    KnpDiagMap map;                // owned cells sorted by dense tag index, chunks of 128
+    int32_t* d_code = nullptr;     // [n_instr*4]
+    double* d_qb = nullptr;        // [n_q*(dim+1)] barycentric points
+    double* d_qw = nullptr;        // [n_q] weights, sum 1
+    double consts[KNP_DIAG_MAX_CONSTS] = {};   // host copy: passed to the kernel by value at every launch
 };
 
 // ---- device-side program ------------------------------------------------------------------
@@ -457,6 +471,7 @@ struct knp_ctx {
     KnpEmi emi;
     KnpStates states;
     std::vector<KnpSamplePlan> sample_plans;   // knp_sample_plan_create: the id is the index; a destroyed slot is reused
+    std::vector<KnpFunctional> functionals;    // knp_functional_create: likewise
     // profiling
     int prof_on = 0;
     std::vector<hipEvent_t> prof_pool;   // recycled timing events

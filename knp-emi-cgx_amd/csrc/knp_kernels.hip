@@ -3101,6 +3101,7 @@ int knp_destroy(knp_ctx* ctx) {
     knp_emi_free(ctx);
     knp_state_free(ctx);
     knp_sample_free(ctx);
+    knp_functional_free(ctx);
     delete ctx;
     return KNP_OK;
 }
@@ -5154,3 +5155,6 @@ int knp_amg_get_level_info(const knp_ctx* ctx, int32_t hier, int32_t level, int3
 
 // membrane state variables: one bytecode program per state, one kernel that steps them all (knp_state_*)
 #include "knp_states.inc"
+
+// volume functionals: per-tag integrals over cells of a bytecode program at the points of a simplex rule (knp_functional_*)
+#include "knp_functional.inc"
