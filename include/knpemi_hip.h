@@ -47,6 +47,9 @@
  *   knp_functional_create / knp_functional_eval
  *        dfx.fem.assemble_scalar(dfx.fem.form(<UFL expression> * dx(tag))) for any expression of the nodal fields, their gradients
  *        and the coordinates: the norms of main.py:70-84 and tests/KNPEMI/electric_potential_norms_*.py, print_conservation, ...
+ *   knp_membrane_functional_create / knp_membrane_functional_eval
+ *        dfx.fem.assemble_scalar(dfx.fem.form(<UFL expression> * dS(tag))) with '+' / '-' restrictions, FacetNormal and normal
+ *        derivatives: the stimulus current of KNPEMIx_solver.py:580-585, the flux forms of utils/calc_fluxes.py:88
  *   knp_emi_*                        the EMI model (src/CGx/EMI): assemble_matrix_block / assemble_vector_block of the forms
  *                                    EMIx_problem.py:152-157, 215-217 and ksp.solve with KSPCG (EMIx_solver.py)
  *   knp_set_comm                     the MPI calls hidden in PETSc/DOLFINx (ghost updates
@@ -83,7 +86,7 @@ extern "C" {
 #define KNP_STATE_MAX_INSTR 768  /* instructions of all state programs together (knp_state_set_program) */
 #define KNP_STATE_MAX_CONSTS 128 /* constants of all state programs together */
 #define KNP_MAX_AMG_LEVELS 16
-#define KNP_FUNCTIONAL_MAX_Q 125 /* quadrature points per cell of a volume functional (knp_functional_create) */
+#define KNP_FUNCTIONAL_MAX_Q 125 /* quadrature points per cell of a volume functional (knp_functional_create) and per facet of a membrane functional */
 
 #define KNP_OK 0
 #define KNP_E_ARG (-1)
@@ -532,6 +535,47 @@ int knp_functional_create(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr /
 int knp_functional_set_constants(knp_ctx* ctx, int32_t id, int32_t n_consts, const double* consts /* host */);
 int knp_functional_eval(knp_ctx* ctx, int32_t id, const knp_fields* fields, double* out /* device [n_tags*n_out] */);
 int knp_functional_destroy(knp_ctx* ctx, int32_t id);
+/* Membrane functionals: per-tag integrals over membrane facets of one bytecode program evaluated at the points of a facet rule, with
+ * one-sided gradients, the facet normal and normal derivatives.  A plan that belongs to the context, like a volume functional (ids
+ * of their own; a destroyed id is reused); several may be live.
+ * knp_membrane_functional_create: a facet map like knp_diag_set_facet_tags (indices into the Gamma list of knp_create, each at most
+ *   once), the rule (q_pts: dim barycentric coordinates per point in the order of the facet's vertices, the vertices of the '+' cell
+ *   without the opposite one; q_w sums to 1), the program with at most KNP_DIAG_MAX_CONSTS constants, and per aux slot its mode:
+ *     -1       the field fields->aux[k] itself, interpolated on the facet
+ *     a        d/dx_a of that field on the intracellular ('+') cell of the facet, a in 0 .. dim-1
+ *     3 + a    d/dx_a on the extracellular ('-') cell
+ *     6 / 7    d/dn on the intracellular / extracellular cell, each along the normal that points out of that cell
+ *     8 + a    component a of the unit normal n_i that points out of the intracellular cell; the slot needs no field pointer
+ *   n_i = -grad(lambda_opp) / |grad(lambda_opp)| with lambda_opp the barycentric coordinate of the intracellular cell's vertex off the
+ *   facet, and n_e = -n_i: the rule and the signs of knp_diag_membrane_fluxes.  Synchronous: builds one record of 32 bytes per listed
+ *   facet (its vertices and the opposite vertex of either cell).  *id receives an id >= 0.
+ * knp_membrane_functional_set_constants: replaces the constants on the host; they travel as kernel arguments of the next evaluation.
+ * knp_membrane_functional_eval: out[t*n_out + j] = sum over the facets F of tag t of |F| sum_q q_w[q] OUT_j(program at point q of F);
+ *   the outputs are not summed together.  KNP_OP_KI a / KNP_OP_KE a / KNP_OP_PHIM read the P1 interpolant of fields->k_i[a] / k_e[a] /
+ *   phi_m at F's vertices (every field is an array over all vertices), KNP_OP_X a the point's coordinate, KNP_OP_AUX k what the slot's
+ *   mode says.  A derivative is sum_{b>=1} g_b (f(v_b) - f(v_0)) over the cell's vertices with v_0 the facet's first vertex and
+ *   g_b = grad(lambda_b)_a or grad(lambda_b) . n, constant on the facet: the gradients come from the coordinates inside the kernel, and
+ *   the differences are taken first, so a field's constant offset costs no digits.  Only the pointers of slots the code reads are
+ *   used.  One facet per lane, 128 per block, the interpreter's register file in LDS (1 KiB per register the program uses, at most
+ *   48 KiB); partials are combined in a fixed order (one wave per tag of at most 64 chunks of 128 facets, one workgroup per longer
+ *   tag): the same bits on every run.  Enqueued on the library's stream; never waits for the device.
+ * knp_membrane_functional_destroy: frees the plan (waits for the stream first); knp_destroy frees the plans that are left.
+ * Errors leave nothing launched and no plan: KNP_E_ARG for a null argument, n_q outside 1 .. KNP_FUNCTIONAL_MAX_Q, n_out outside
+ *   1 .. 3, n_aux outside 0 .. KNP_MAX_AUX, a mode outside -1 .. 10 or with an axis >= dim, an invalid or empty program, one that
+ *   reads an aux slot >= n_aux or writes an output >= n_out, more than KNP_DIAG_MAX_CONSTS constants or another count in
+ *   set_constants, an unknown id, a facet out of range or listed twice, a seg_ptr that does not start at 0 or decreases, in eval a
+ *   null pointer of a slot the code reads; KNP_E_MESH (checked on the host at create, for the slots the code reads) when a mode of
+ *   the extracellular cell (3 .. 5, 7) is bound and a listed facet's extracellular cell does not hold it, or when a geometric mode
+ *   (>= 0) is bound and a cell it reads is flat (zero determinant, or gradients that are not finite; mode 7 and the normal read the
+ *   intracellular cell).  n_tags == 0 is a successful no-op. */
+int knp_membrane_functional_create(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr /* host [n_tags+1] */,
+                                   const int32_t* facets /* host [seg_ptr[n_tags]] */, int32_t n_q, const double* q_pts /* host [n_q*dim] */,
+                                   const double* q_w /* host [n_q] */, int32_t n_instr, const int32_t* code /* host [n_instr*4] */,
+                                   int32_t n_consts, const double* consts /* host */, int32_t n_aux, const int32_t* aux_mode /* host [n_aux] */,
+                                   int32_t n_out /* 1..3 */, int32_t* id /* host */);
+int knp_membrane_functional_set_constants(knp_ctx* ctx, int32_t id, int32_t n_consts, const double* consts /* host */);
+int knp_membrane_functional_eval(knp_ctx* ctx, int32_t id, const knp_fields* fields, double* out /* device [n_tags*n_out] */);
+int knp_membrane_functional_destroy(knp_ctx* ctx, int32_t id);
 
 /* ---- the EMI model: two potentials with constant conductivities, ONE unknown per node (reference src/CGx/EMI) ----
  * Unknown n is node n of knp_get_layout; every vector is a device array of n_nodes_owned doubles.  One GPU only: every call

@@ -147,6 +147,11 @@ SIGNATURES = {
     "knp_functional_set_constants": (C.c_int, [vp, C.c_int32, C.c_int32, f64p]),
     "knp_functional_eval": (C.c_int, [vp, C.c_int32, C.POINTER(Fields), vp]),
     "knp_functional_destroy": (C.c_int, [vp, C.c_int32]),
+    "knp_membrane_functional_create": (C.c_int, [vp, C.c_int32, i32p, i32p, C.c_int32, f64p, f64p, C.c_int32, i32p, C.c_int32, f64p, C.c_int32,
+                                                 i32p, C.c_int32, i32p]),
+    "knp_membrane_functional_set_constants": (C.c_int, [vp, C.c_int32, C.c_int32, f64p]),
+    "knp_membrane_functional_eval": (C.c_int, [vp, C.c_int32, C.POINTER(Fields), vp]),
+    "knp_membrane_functional_destroy": (C.c_int, [vp, C.c_int32]),
     "knp_emi_setup": (C.c_int, [vp, C.c_double, C.c_double, C.c_double, C.c_double]),
     "knp_emi_get_csr": (C.c_int, [vp, i32p, i32p, f64p]),
     "knp_emi_set_dirichlet": (C.c_int, [vp, C.c_int32, i32p]),

@@ -402,6 +402,16 @@ class ProblemEMI(MixedDimensionalProblem):
         from .functionals import assemble_scalar
         return assemble_scalar(self, integrand_i, integrand_e, tags, degree)
 
+    def assemble_scalar_membrane(self, integrand, tags=None, degree=10):
+        """``dfx.fem.assemble_scalar(dfx.fem.form(integrand * dS(tags)))``: the integral of ``integrand`` over the membrane tags
+        (default every tag of ``gamma_tags``), summed over the tags, with a facet rule exact to ``degree``.  Besides what
+        ``assemble_scalar`` takes (every Function is an aux field here) the integrand may hold restricted derivatives (``fem.grad(f)[a]('+')``: the intracellular cell,
+        ``('-')``: the extracellular one), ``fem.FacetNormal`` and ``fem.NormalDerivative`` / ``fem.dot``.  A float for a single
+        expression, else an array.  One launch pair (knp_membrane_functional_eval) and one read-back; keep a
+        ``functionals.MembraneFunctional`` to integrate again or to have the rows per tag."""
+        from .functionals import assemble_scalar_membrane
+        return assemble_scalar_membrane(self, integrand, tags, degree)
+
     def setup_preconditioner(self):
         """The preconditioner matrix is the EMI matrix itself (with the Dirichlet elimination).  The reference's P = sigma K + M per side
         (EMIx_problem.py:225-248) is nearly singular per side in SI units and is not built."""

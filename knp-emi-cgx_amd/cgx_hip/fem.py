@@ -10,7 +10,9 @@ Semantics kept from UFL on purpose:
   * ``bool(expr)`` is True for every expression (UFL ``Expr.__bool__``) -- this is what makes the
     reference's ``IonicModel.f_NKCC1`` return zero (KNPEMIx_ionic_model.py:62-69).
   * ``expr('+')`` / ``expr('-')`` restrictions are accepted and are no-ops: all coefficients are
-    continuous P1 fields, only facet-vertex values enter a Gamma integral.
+    continuous P1 fields, only facet-vertex values enter a Gamma integral.  The exceptions are the nodes that have two
+    values on a membrane facet -- ``Derivative``, ``NormalComponent``, ``NormalDerivative`` -- which keep the side for the
+    integrands of membrane functionals (cgx_hip/functionals.py).
 """
 from __future__ import annotations
 
@@ -136,14 +138,51 @@ class Op(Expr):
         self.op, self.args, self.imm = op, tuple(args), imm
 
 
-class Derivative(Expr):
-    """d/dx_axis of a P1 ``Function``: constant on every cell.  Only the integrands of volume functionals may hold one
-    (cgx_hip/functionals.py); membrane and state programs are evaluated at vertices and facets, where it has no single value."""
+def _restriction(r):
+    if r not in ("+", "-"):
+        raise ValueError(f"a restriction is '+' (the intracellular cell of the facet) or '-' (the extracellular one), not {r!r}")
+    return r
 
-    def __init__(self, function, axis):
+
+class Derivative(Expr):
+    """d/dx_axis of a P1 ``Function``: constant on every cell.  The integrands of volume functionals may hold one
+    (cgx_hip/functionals.py), and so may those of membrane functionals: on a membrane facet the two adjacent cells give two
+    values, and ``d('+')`` / ``d('-')`` is the restricted copy that takes the one of the intracellular / extracellular cell (UFL's
+    restriction; ``side`` None: unrestricted).  A volume functional ignores the restriction.  Membrane and state programs are
+    evaluated at vertices, where a derivative has no value at all, and refuse it."""
+
+    def __init__(self, function, axis, side=None):
         if not isinstance(function, Function):
             raise TypeError("grad() takes a Function (a P1 nodal field)")
-        self.function, self.axis = function, int(axis)
+        self.function, self.axis, self.side = function, int(axis), side
+
+    def __call__(self, restriction=None):
+        return self if restriction is None else Derivative(self.function, self.axis, _restriction(restriction))
+
+
+class NormalComponent(Expr):
+    """Component ``axis`` of the unit normal of a membrane facet (``FacetNormal``): ``n[a]('+')`` points out of the intracellular
+    cell, ``n[a]('-')`` is its negative.  Only membrane functionals take it, and only restricted."""
+
+    def __init__(self, axis, side=None):
+        self.axis, self.side = int(axis), side
+
+    def __call__(self, restriction=None):
+        return self if restriction is None else NormalComponent(self.axis, _restriction(restriction))
+
+
+class NormalDerivative(Expr):
+    """d f / d n_side of a P1 ``Function`` on a membrane facet: the gradient on that side's cell times that side's outward normal.
+    One aux slot of a membrane functional, where ``inner(grad(f)(side), n(side))`` takes ``dim`` slots for the gradient and
+    ``dim`` for the normal.  ``side`` None: the function's own side (a solution function of the problem)."""
+
+    def __init__(self, function, side=None):
+        if not isinstance(function, Function):
+            raise TypeError("NormalDerivative() takes a Function (a P1 nodal field)")
+        self.function, self.side = function, None if side is None else _restriction(side)
+
+    def __call__(self, restriction=None):
+        return self if restriction is None else NormalDerivative(self.function, restriction)
 
 
 def as_expr(v):
@@ -194,6 +233,26 @@ def inner(a, b):
     return total
 
 
+def FacetNormal(mesh):
+    """``ufl.FacetNormal``: the list of the ``dim`` components of a membrane facet's unit normal, to be restricted"""
+    return [NormalComponent(a) for a in range(mesh.geometry.dim)]
+
+
+def dot(a, b):
+    """``ufl.dot``: ``inner`` for two scalars or two lists -- and where one list is ``grad(f)`` restricted to r (all components, axes in
+    order) and the other the facet normal restricted to r', the single node +-``NormalDerivative(f, r)``, + for r == r'"""
+    if isinstance(a, (list, tuple)) and isinstance(b, (list, tuple)) and len(a) == len(b) and len(a):
+        for g, n in ((a, b), (b, a)):
+            if (all(isinstance(x, Derivative) for x in g) and all(isinstance(x, NormalComponent) for x in n)
+                    and all(x.function is g[0].function and x.side == g[0].side and x.axis == k for k, x in enumerate(g))
+                    and all(x.side == n[0].side and x.axis == k for k, x in enumerate(n))
+                    and g[0].side is not None and n[0].side is not None
+                    and len(g) == g[0].function.function_space.mesh.geometry.dim):
+                d = NormalDerivative(g[0].function, g[0].side)
+                return d if g[0].side == n[0].side else -d
+    return inner(a, b)
+
+
 max = max_value      # noqa: A001  (the reference spells it ufl.max / ufl.min)
 min = min_value      # noqa: A001
 
@@ -230,12 +289,22 @@ class AuxSlotsExhausted(ValueError):
     """the expressions of one program read more than KNP_MAX_AUX nodal fields (and derivatives) that need an aux slot"""
 
 
-def compile_program(outputs, field_roles, aux_functions=None, aux_derivs=None):
+# aux_derivs codes of a membrane functional besides -1 and the axes 0..2 (there: on the intracellular cell of the facet)
+MODE_GRAD_E, MODE_DN_I, MODE_NORMAL = 3, 6, 8
+
+
+def compile_program(outputs, field_roles, aux_functions=None, aux_derivs=None, facet_sides=None):
     """outputs: list of 3 expressions (I_ch^k).  field_roles: dict id(Function) -> ('KI', j) |
     ('KE', j) | ('PHIM', 0).  Other Functions get aux slots (shared list ``aux_functions``).
     ``aux_derivs``: a list that runs parallel to ``aux_functions`` (-1: the slot holds the Function's value, a: its derivative
     d/dx_a) lets the expressions hold ``Derivative`` nodes: each (Function, axis) pair takes one slot.  Without it a
-    ``Derivative`` is refused, as in every membrane and state program."""
+    ``Derivative`` is refused, as in every membrane and state program.
+    ``facet_sides`` (with ``aux_derivs``): dict id(Function) -> 0 | 1, the side a solution function lives on, asks for the programs
+    of membrane functionals.  The codes of ``aux_derivs`` are then a + 3 s for d/dx_a on the cell of side s (0 intracellular '+',
+    1 extracellular '-'), 6 + s for ``NormalDerivative`` on side s, 8 + a for component a of the intracellular outward normal
+    (such a slot has no Function: None in ``aux_functions``; ``n[a]('-')`` negates it).  A function listed in ``facet_sides``
+    defaults to its side and refuses the other; anything else must be restricted.  Without ``facet_sides`` a restriction on a
+    ``Derivative`` is ignored and normals and normal derivatives are a ValueError."""
     aux_functions = aux_functions if aux_functions is not None else []
     if aux_derivs is not None and len(aux_derivs) != len(aux_functions):
         raise ValueError("aux_derivs must have one entry per aux function")
@@ -250,6 +319,20 @@ def compile_program(outputs, field_roles, aux_functions=None, aux_derivs=None):
         if aux_derivs is not None:
             aux_derivs.append(axis)
         return len(aux_functions) - 1
+
+    def side_of(e):
+        """0 | 1: the cell of the facet a derivative node of a membrane functional is taken on"""
+        own = facet_sides.get(id(e.function))
+        if e.side is None:
+            if own is None:
+                raise ValueError(f"a derivative of '{e.function.name}' on a membrane facet must be restricted, ('+') for the "
+                                 "intracellular cell or ('-') for the extracellular one: only the solution functions have a side of their own")
+            return own
+        s = 0 if e.side == "+" else 1
+        if own is not None and own != s:
+            raise ValueError(f"'{e.function.name}' lives on the {'intra' if own == 0 else 'extra'}cellular side: its derivative "
+                             f"cannot be restricted to ('{e.side}')")
+        return s
     nodes = []                # SSA list: (opname, argidx tuple, imm)
     index = {}                # structural key -> ssa id
     consts = []
@@ -288,8 +371,21 @@ def compile_program(outputs, field_roles, aux_functions=None, aux_derivs=None):
                 role = ("AUX", aux_slot(e, -1))
             return emit(role, (role[0], (), role[1]))
         if isinstance(e, Derivative) and aux_derivs is not None:
-            role = ("AUX", aux_slot(e.function, e.axis))
+            role = ("AUX", aux_slot(e.function, e.axis + (MODE_GRAD_E * side_of(e) if facet_sides is not None else 0)))
             return emit(role, (role[0], (), role[1]))
+        if isinstance(e, (NormalDerivative, NormalComponent)) and aux_derivs is not None:
+            if facet_sides is None:
+                raise ValueError("a facet normal or a normal derivative has a value on membrane facets only: "
+                                 "volume functionals, membrane and state programs do not take it")
+            if isinstance(e, NormalDerivative):
+                role = ("AUX", aux_slot(e.function, MODE_DN_I + side_of(e)))
+                return emit(role, (role[0], (), role[1]))
+            if e.side is None:
+                raise ValueError("the facet normal must be restricted: n[a]('+') points out of the intracellular cell, n[a]('-') out "
+                                 "of the extracellular one")
+            role = ("AUX", aux_slot(None, MODE_NORMAL + e.axis))
+            n = emit(role, (role[0], (), role[1]))
+            return n if e.side == "+" else emit(("NEG", (n,), 0), ("NEG", (n,), 0))
         if isinstance(e, Op):
             args = tuple(visit(a) for a in e.args)
             return emit((e.op, args, e.imm), (e.op, args, e.imm))
@@ -439,7 +535,9 @@ def compile_state_program(state, field_roles, aux_functions):
 # ------------------------------------------------------------------------------------------
 def evaluate_numpy(e, env):
     """Evaluate an expression with NumPy. env: {'x': [arrays per axis], 'fields': {id(Function): array}} and, for expressions
-    with derivatives, 'grads': {(id(Function), axis): array}."""
+    with derivatives, 'grads': {(id(Function), axis): array}.  On membrane facets: 'grads' may also hold (id, axis, '+' | '-') for a
+    restricted derivative (it falls back to the unrestricted key), 'normal_derivs': {(id(Function), '+' | '-' | None): array} and
+    'normal': [arrays per axis], the intracellular outward normal n('+')."""
     e = as_expr(e)
     if isinstance(e, (Literal,)):
         return e.value
@@ -452,7 +550,14 @@ def evaluate_numpy(e, env):
     if isinstance(e, Function):
         return env["fields"][id(e)]
     if isinstance(e, Derivative):
-        return env["grads"][(id(e.function), e.axis)]
+        key = (id(e.function), e.axis, e.side)
+        return env["grads"][key if e.side is not None and key in env["grads"] else key[:2]]
+    if isinstance(e, NormalDerivative):
+        return env["normal_derivs"][(id(e.function), e.side)]
+    if isinstance(e, NormalComponent):
+        if e.side is None:
+            raise ValueError("the facet normal must be restricted")
+        return env["normal"][e.axis] if e.side == "+" else -env["normal"][e.axis]
     a = [evaluate_numpy(x, env) for x in e.args]
     op = e.op
     if op == "ADD": return a[0] + a[1]

@@ -8,6 +8,11 @@ the cells of the chosen tags sorted by tag, and then evaluates it at the points 
 side, into a device tensor, without a host copy or a synchronisation.  Time-dependent Constants are read anew at every call.
 
 ``compile_functional`` is the host part (expression -> programs, tags -> cell lists, degree -> rule); it needs no device.
+
+``MembraneFunctional`` is the same over membrane tags (csrc/knp_membrane_functional.inc, ``knp_membrane_functional_*``): the
+reference's ``assemble_scalar(form(<UFL expression> * dS(tag)))``.  There an integrand may also hold restricted derivatives
+(``fem.grad(f)[a]('+')``), the facet normal (``fem.FacetNormal``) and normal derivatives (``fem.NormalDerivative``, ``fem.dot``);
+``compile_membrane_functional`` is its host part.
 """
 from __future__ import annotations
 
@@ -58,7 +63,7 @@ def _functions_of(e, found):
     e = fem.as_expr(e)
     if isinstance(e, fem.Function):
         found.append(e)
-    elif isinstance(e, fem.Derivative):
+    elif isinstance(e, (fem.Derivative, fem.NormalDerivative)):
         found.append(e.function)
     elif isinstance(e, fem.Op):
         for a in e.args:
@@ -243,6 +248,173 @@ class VolumeFunctional:
 def assemble_scalar(problem, integrand_i=None, integrand_e=None, tags=None, degree=2):
     """what ``ProblemKNPEMI.assemble_scalar`` and ``ProblemEMI.assemble_scalar`` do: one functional, one evaluation, the sum over tags"""
     F = VolumeFunctional(problem, integrand_i, integrand_e, tags, degree)
+    try:
+        tot = F.total()
+    finally:
+        F.close()
+    return float(tot[0]) if F.spec.single else tot
+
+
+# ------------------------------------------------------------------------------------------ membrane functionals
+MEMBRANE_FEATURE = "membrane functionals (MembraneFunctional / assemble_scalar_membrane / add_functional)"
+
+
+def membrane_field_roles(problem):
+    """``field_roles`` and, on a KNP-EMI problem, ``phi_m_prev`` as ``PHIM``: the roles of the membrane programs"""
+    roles = field_roles(problem)
+    if roles and getattr(problem, "phi_m_prev", None) is not None:
+        roles[id(problem.phi_m_prev)] = ("PHIM", 0)
+    return roles
+
+
+class MembraneFunctionalSpec:
+    """What ``compile_membrane_functional`` returns: ``spec`` (the ``fem.ProgramSpec``; ``aux_derivs`` are the slot modes of
+    knp_membrane_functional_create, ``aux_functions`` has None for a normal component), the rule ``q_pts`` / ``q_w``, ``n_out``,
+    ``single``, and per row of the result ``groups`` (tuples of membrane tags), ``tags`` (each group's first tag) and ``area``, with
+    the facet map ``seg_ptr`` / ``facets`` (indices into the problem's gamma list)."""
+
+
+def compile_membrane_functional(problem, integrand, tags=None, degree=10):
+    from .diagnostics import FacetGroupLayout
+    from .mesh import facet_quadrature
+    p = problem
+    dim = p.local_mesh.coords.shape[1]
+    single = not isinstance(integrand, (list, tuple))
+    outs = [fem.as_expr(e) for e in ([integrand] if single else integrand)]
+    if not 1 <= len(outs) <= MAX_OUTPUTS:
+        raise ValueError(f"an integrand is one expression or a list of up to {MAX_OUTPUTS}")
+    known = [int(t) for t in p.gamma_tags]
+    groups = [(t,) for t in known] if tags is None else [tuple(int(t) for t in g) if isinstance(g, (list, tuple)) else (int(g),)
+                                                        for g in tags]
+    listed = [t for g in groups for t in g]
+    if len(set(listed)) != len(listed):
+        raise ValueError("a membrane tag is listed twice")
+    for g in groups:
+        if not g:
+            raise ValueError("an empty group of membrane tags")
+        for t in g:
+            if t not in known:
+                raise ValueError(f"unknown membrane tag {t}: the problem has the membrane tags {known}")
+    if int(degree) != degree or degree < 0:
+        raise ValueError("degree must be a non-negative integer")
+    n_q = (int(degree) // 2 + 1) ** (dim - 1)
+    if n_q > _lib.KNP_FUNCTIONAL_MAX_Q:
+        raise ValueError(f"degree {degree} needs {n_q} quadrature points per facet, more than {_lib.KNP_FUNCTIONAL_MAX_Q}")
+    sides = {id(f): s for s in range(2) for f in _side_functions(p, s)}
+    aux, modes = [], []
+    try:
+        prog = fem.compile_program(outs, membrane_field_roles(p), aux, modes, facet_sides=sides)
+    except fem.AuxSlotsExhausted:
+        raise ValueError(f"the integrand binds more than {_lib.KNP_MAX_AUX} fields, derivatives and normal components to aux slots") from None
+    if len(prog.const_sources) > _lib.KNP_DIAG_MAX_CONSTS:
+        raise ValueError(f"the integrand has more than {_lib.KNP_DIAG_MAX_CONSTS} constants")
+    lay = FacetGroupLayout(p, groups)
+    spec = MembraneFunctionalSpec()
+    q_pts, q_w = facet_quadrature(dim, int(degree))
+    spec.q_pts, spec.q_w = np.ascontiguousarray(q_pts, dtype=np.float64), np.ascontiguousarray(q_w, dtype=np.float64)
+    spec.spec, spec.n_out, spec.single, spec.degree = prog, len(outs), single, int(degree)
+    spec.groups, spec.tags, spec.area, spec.seg_ptr, spec.facets = lay.groups, lay.tags, lay.area, lay.seg_ptr, lay.facets
+    return spec
+
+
+class MembraneFunctional:
+    """Per membrane tag, the integral of ``integrand`` over that tag's facets with a facet rule exact to polynomial ``degree`` (10:
+    the problem's own ``q_pts``).  The integrand is one expression or a list of up to three; besides what a volume functional
+    takes it may hold ``fem.grad(f)[a]('+' | '-')``, ``fem.FacetNormal(mesh)[a]('+' | '-')``, ``fem.NormalDerivative(f, side)`` and
+    ``fem.dot``: '+' is the intracellular cell of a facet, '-' the extracellular one.  ``tags``: None for every tag of
+    ``problem.gamma_tags``, each on its own, or a list whose entries are tags or tuples of tags pooled into one row.  ``groups`` /
+    ``tags`` (each row's first tag) / ``area``: per row of the result.  A call returns the device tensor [n_tags, n_out]."""
+
+    def __init__(self, problem, integrand, tags=None, degree=10):
+        self.problem = problem
+        self.id = None
+        spec = self.spec = compile_membrane_functional(problem, integrand, tags, degree)
+        self.tags, self.groups, self.area, self.n_out, self.degree = spec.tags, spec.groups, spec.area, spec.n_out, spec.degree
+        if problem.comm.size > 1:
+            raise NotImplementedError(f"{MEMBRANE_FEATURE} run on one rank: a functional integrates this rank's owned facets only and "
+                                      "the sum over ranks is not implemented")
+        be = self.backend = _backend(problem)
+        self.n_vertices = problem.local_mesh.coords.shape[0]
+        i32, f64 = (lambda a: a.ctypes.data_as(_lib.i32p)), (lambda a: a.ctypes.data_as(_lib.f64p))
+        prog = spec.spec
+        code = np.ascontiguousarray(prog.code, dtype=np.int32)
+        consts = prog.constants()
+        modes = np.ascontiguousarray(prog.aux_derivs, dtype=np.int32)
+        fid = C.c_int32(-1)
+        be.check(be.lib.knp_membrane_functional_create(be.ctx, len(spec.tags), i32(spec.seg_ptr), i32(spec.facets) if spec.facets.size else None,
+                                                       len(spec.q_w), f64(spec.q_pts), f64(spec.q_w), code.shape[0], i32(code), consts.shape[0],
+                                                       f64(consts) if consts.size else None, modes.shape[0], i32(modes) if modes.size else None,
+                                                       spec.n_out, C.byref(fid)))
+        self.id = int(fid.value)
+        self._fields()      # refuses a Function that is not a nodal field of this mesh now, not at the first call
+
+    def _fields(self):
+        """the ABI's struct of device pointers, filled at every call: a Function whose ``x.array`` was bound to another tensor in
+        between is read where it is now"""
+        p = self.problem
+        f = _lib.Fields()
+        roles = membrane_field_roles(p)
+        if roles:
+            for fn in list(p.wh[0]) + list(p.wh[1]) + [p.phi_m_prev]:
+                role = roles.get(id(fn))
+                if role is None:
+                    continue
+                if role[0] == "PHIM":
+                    f.phi_m = fn.data_ptr()
+                else:
+                    (f.k_i if role[0] == "KI" else f.k_e)[role[1]] = fn.data_ptr()
+        for k, fn in enumerate(self.spec.spec.aux_functions):
+            if fn is None:      # a normal component
+                continue
+            t = fn.x.array
+            if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.numel() != self.n_vertices:
+                raise ValueError(f"'{fn.name}' is not a nodal field of this problem's mesh on the device")
+            f.aux[k] = fn.data_ptr()
+        return f
+
+    def close(self):
+        """free the plan's device memory (also done when the functional or its problem's context goes away)"""
+        be, fid = getattr(self, "backend", None), getattr(self, "id", None)
+        self.id = None
+        if fid is not None and be is not None and getattr(be, "ctx", None):
+            be.lib.knp_membrane_functional_destroy(be.ctx, fid)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:      # noqa: BLE001
+            pass
+
+    def __call__(self, out=None):
+        """The integrals per row, [n_tags, n_out] on the device; the constants and the tensors' addresses are read anew.  Enqueued:
+        no host copy, no synchronisation.  ``out``: a contiguous float64 device tensor of that size, else a new one."""
+        be = self.backend
+        if self.id is None:
+            raise _lib.KnpError("the functional is closed")
+        shape = (len(self.tags), self.n_out)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=be.device)
+        if not (out.is_contiguous() and out.dtype == torch.float64 and out.is_cuda and out.numel() == shape[0] * shape[1]):
+            raise ValueError(f"out must be a contiguous float64 device tensor of {shape[0]} x {shape[1]} entries")
+        f = self._fields()
+        consts = self.spec.spec.constants()
+        if consts.size:
+            be.check(be.lib.knp_membrane_functional_set_constants(be.ctx, self.id, consts.shape[0], consts.ctypes.data_as(_lib.f64p)))
+        be.check(be.lib.knp_membrane_functional_eval(be.ctx, self.id, C.byref(f), C.c_void_p(out.data_ptr())))
+        return out.view(shape)
+
+    def value(self):
+        """the integrals per row as NumPy [n_tags, n_out] (one read-back)"""
+        return self().cpu().numpy()
+
+    def total(self):
+        """the sum over the rows, [n_out]"""
+        return self.value().sum(axis=0)
+
+
+def assemble_scalar_membrane(problem, integrand, tags=None, degree=10):
+    """what ``assemble_scalar_membrane`` of both problem classes does: one functional, one evaluation, the sum over the rows"""
+    F = MembraneFunctional(problem, integrand, tags, degree)
     try:
         tot = F.total()
     finally:

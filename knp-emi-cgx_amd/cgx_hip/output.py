@@ -598,12 +598,14 @@ class RunOutput:
 
     def save_functionals(self):
         """Per ``add_functional`` entry: functional_<name>.npy [records, n_tags, n_out] at steps 0, interval, 2 interval, ...;
-        functional_<name>_tags.npy: per row (tag, side 0 intra / 1 extra, volume).  One read-back per functional."""
+        functional_<name>_tags.npy: per row (tag, side 0 intra / 1 extra, volume), for a membrane functional (the row's first tag,
+        side 2, area).  One read-back per functional."""
         out = self.p.output_dir
         for g in self.functionals:
             F = g["F"]
             np.save(out + f"functional_{g['name']}.npy", g["buf"].cpu().numpy())
-            np.save(out + f"functional_{g['name']}_tags.npy", np.stack([F.tags, F.side, F.volume], axis=1).astype(np.float64))
+            rows = [F.tags, F.side, F.volume] if hasattr(F, "side") else [F.tags, np.full(len(F.tags), 2), F.area]
+            np.save(out + f"functional_{g['name']}_tags.npy", np.stack(rows, axis=1).astype(np.float64))
 
     def figures(self):
         """PNG plots of the traces (KNPEMIx_solver.py:645-764) when matplotlib is installed; the data are exported either way."""

@@ -880,6 +880,16 @@ class ProblemKNPEMI(MixedDimensionalProblem):
         from .functionals import assemble_scalar
         return assemble_scalar(self, integrand_i, integrand_e, tags, degree)
 
+    def assemble_scalar_membrane(self, integrand, tags=None, degree=10):
+        """``dfx.fem.assemble_scalar(dfx.fem.form(integrand * dS(tags)))``: the integral of ``integrand`` over the membrane tags
+        (default every tag of ``gamma_tags``), summed over the tags, with a facet rule exact to ``degree``.  Besides what
+        ``assemble_scalar`` takes the integrand may hold restricted derivatives (``fem.grad(f)[a]('+')``: the intracellular cell,
+        ``('-')``: the extracellular one), ``fem.FacetNormal`` and ``fem.NormalDerivative`` / ``fem.dot``.  A float for a single
+        expression, else an array.  One launch pair (knp_membrane_functional_eval) and one read-back; keep a
+        ``functionals.MembraneFunctional`` to integrate again or to have the rows per tag."""
+        from .functionals import assemble_scalar_membrane
+        return assemble_scalar_membrane(self, integrand, tags, degree)
+
     def print_conservation(self):
         """Total ion amounts and, per intracellular tag, volume, membrane area and charge: the reference's lines
         (KNPEMIx_problem.py:807-843), printed on rank 0 from ``ion_budget()``."""

@@ -128,7 +128,7 @@ class SolverKNPEMI:
         self.sample_grids, self.sample_interval = parse_sample_grids(out, problem.local_mesh.coords.shape[1], float(problem.mesh_conversion_factor),
                                                                      int(self.save_interval), int(self.time_steps))
         self.out_file_prefix = problem.output_dir
-        self.functionals = []      # add_functional(): (name, VolumeFunctional, interval)
+        self.functionals = []      # add_functional(): (name, VolumeFunctional | MembraneFunctional, interval)
         self.direct_solver = bool(solver_config["direct"])
         self.view_input = solver_config.get("view_ksp", False)
         norm_set = False
@@ -577,17 +577,18 @@ class SolverKNPEMI:
             self.export_data()
 
     def add_functional(self, name, F, interval=1):
-        """Record the ``VolumeFunctional`` ``F`` (cgx_hip/functionals.py) at step 0 and at every ``interval``-th step, on the device and
-        without a host wait; the run ends with functional_<name>.npy [records, n_tags, n_out] and functional_<name>_tags.npy (tag,
-        side, volume per row).  Call it before ``solve()`` / ``prepare()``."""
-        from .functionals import VolumeFunctional
+        """Record the ``VolumeFunctional`` or ``MembraneFunctional`` ``F`` (cgx_hip/functionals.py) at step 0 and at every
+        ``interval``-th step, on the device and without a host wait; the run ends with functional_<name>.npy [records, n_tags, n_out]
+        and functional_<name>_tags.npy (per row: tag, side, volume -- for a membrane functional the row's first tag, side 2 and the
+        area).  Call it before ``solve()`` / ``prepare()``."""
+        from .functionals import MembraneFunctional, VolumeFunctional
         if getattr(self, "_prepared", False):
             raise RuntimeError("add_functional() must be called before solve()")
         name = str(name)
         if not name or any(name == n for n, _, _ in self.functionals):
             raise ValueError(f"a functional needs a name of its own (got '{name}')")
-        if not isinstance(F, VolumeFunctional) or F.problem is not self.problem:
-            raise ValueError("add_functional() takes a VolumeFunctional of this solver's problem")
+        if not isinstance(F, (VolumeFunctional, MembraneFunctional)) or F.problem is not self.problem:
+            raise ValueError("add_functional() takes a VolumeFunctional or a MembraneFunctional of this solver's problem")
         if int(interval) < 1:
             raise ValueError("interval must be at least 1")
         self.functionals.append((name, F, int(interval)))

@@ -3102,6 +3102,7 @@ int knp_destroy(knp_ctx* ctx) {
     knp_state_free(ctx);
     knp_sample_free(ctx);
     knp_functional_free(ctx);
+    knp_membrane_functional_free(ctx);
     delete ctx;
     return KNP_OK;
 }
@@ -5158,3 +5159,5 @@ int knp_amg_get_level_info(const knp_ctx* ctx, int32_t hier, int32_t level, int3
 
 // volume functionals: per-tag integrals over cells of a bytecode program at the points of a simplex rule (knp_functional_*)
 #include "knp_functional.inc"
+// membrane functionals: per-tag integrals over membrane facets of a bytecode program with one-sided gradients and the normal
+#include "knp_membrane_functional.inc"
