@@ -16,6 +16,7 @@ reference's ``assemble_scalar(form(<UFL expression> * dS(tag)))``.  There an int
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import math
 
@@ -26,6 +27,7 @@ from . import _lib, fem
 from .diagnostics import cell_volumes, tag_map
 
 FEATURE = "volume functionals (VolumeFunctional / assemble_scalar / add_functional)"
+MEMBRANE_FEATURE = "membrane functionals (MembraneFunctional / assemble_scalar_membrane / add_functional)"
 MAX_OUTPUTS = 3
 
 
@@ -145,9 +147,9 @@ def compile_functional(problem, integrand_i=None, integrand_e=None, tags=None, d
     return spec
 
 
-def _backend(problem):
+def _backend(problem, feature, items):
     if problem.comm.size > 1:
-        raise NotImplementedError(f"{FEATURE} run on one rank: a functional integrates this rank's owned cells only and the sum over "
+        raise NotImplementedError(f"{feature} run on one rank: a functional integrates this rank's owned {items} only and the sum over "
                                   "ranks is not implemented")
     be = getattr(problem, "backend", None)
     if be is None:
@@ -157,44 +159,51 @@ def _backend(problem):
     return be
 
 
-class VolumeFunctional:
-    """Per cell tag, the integral of ``integrand_i`` (intracellular tags) or ``integrand_e`` (extracellular tags) with a rule exact to
-    polynomial ``degree``.  Each integrand is one expression or a list of up to three (both sides the same number); ``tags``: None
-    for every cell tag of the sides that have an integrand.  ``tags`` / ``side`` / ``volume``: per row of the result -- the
-    intracellular tags first, each side's in the order given.  A call returns the device tensor [n_tags, n_out]."""
+Plan = collections.namedtuple("Plan", "id spec first n_rows")      # a plan of the library, its fem.ProgramSpec and the rows it writes
 
-    def __init__(self, problem, integrand_i=None, integrand_e=None, tags=None, degree=2):
-        self.problem = problem
-        self.ids = []
-        spec = self.spec = compile_functional(problem, integrand_i, integrand_e, tags, degree)
-        self.tags, self.side, self.volume, self.n_out, self.degree = spec.tags, spec.side, spec.volume, spec.n_out, spec.degree
-        be = self.backend = _backend(problem)
+
+class _Functional:
+    """What the two kinds share.  A functional holds ``plans``: a volume functional one per side, a membrane functional one.  A kind
+    names its entry points of the library (``ABI``), what it integrates over (``FEATURE``, ``ITEMS``) and its role map (``roles``);
+    its constructor sets ``spec``, ``tags``, ``n_out`` and its own per-row attributes, calls ``_open`` and then ``_create`` per plan."""
+
+    def _open(self, problem):
+        self.problem, self.plans, self.n_plans = problem, [], 0
+        self.backend = _backend(problem, self.FEATURE, self.ITEMS)
         self.n_vertices = problem.local_mesh.coords.shape[0]
+
+    def _create(self, prog, n_rows, seg_ptr, items, q_pts, q_w):
+        """one plan for the next ``n_rows`` rows: the items of every row (``seg_ptr`` into ``items``), the rule and the program"""
+        be = self.backend
         i32, f64 = (lambda a: a.ctypes.data_as(_lib.i32p)), (lambda a: a.ctypes.data_as(_lib.f64p))
-        for sp in spec.sides:
-            prog = sp.spec
-            code = np.ascontiguousarray(prog.code, dtype=np.int32)
-            consts = prog.constants()
-            derivs = np.ascontiguousarray(prog.aux_derivs, dtype=np.int32)
-            fid = C.c_int32(-1)
-            be.check(be.lib.knp_functional_create(be.ctx, len(sp.tags), i32(sp.seg_ptr), i32(sp.cells) if sp.cells.size else None,
-                                                  len(spec.q_w), f64(spec.q_bary), f64(spec.q_w), code.shape[0], i32(code), consts.shape[0],
-                                                  f64(consts) if consts.size else None, derivs.shape[0], i32(derivs) if derivs.size else None,
-                                                  spec.n_out, C.byref(fid)))
-            self.ids.append(int(fid.value))
-            self._fields(prog)      # refuses a Function that is not a nodal field of this mesh now, not at the first call
+        code = np.ascontiguousarray(prog.code, dtype=np.int32)
+        consts = prog.constants()
+        modes = np.ascontiguousarray(prog.aux_derivs, dtype=np.int32)
+        fid = C.c_int32(-1)
+        be.check(getattr(be.lib, self.ABI + "_create")(be.ctx, n_rows, i32(seg_ptr), i32(items) if items.size else None, len(q_w), f64(q_pts),
+                                                       f64(q_w), code.shape[0], i32(code), consts.shape[0], f64(consts) if consts.size else None,
+                                                       modes.shape[0], i32(modes) if modes.size else None, self.n_out, C.byref(fid)))
+        self.plans.append(Plan(int(fid.value), prog, sum(pl.n_rows for pl in self.plans), n_rows))
+        self.n_plans = len(self.plans)
+        self._fields(prog)      # refuses a Function that is not a nodal field of this mesh now, not at the first call
 
     def _fields(self, prog):
-        """the ABI's struct of device pointers for one side's program, filled at every call: a Function whose ``x.array`` was
-        bound to another tensor in between is read where it is now"""
+        """the ABI's struct of device pointers for one program, filled at every call: a Function whose ``x.array`` was bound to
+        another tensor in between is read where it is now"""
         p = self.problem
         f = _lib.Fields()
-        roles = field_roles(p)
-        for fn in (list(p.wh[0]) + list(p.wh[1]) if roles else []):
+        roles = self.roles(p)
+        for fn in (list(p.wh[0]) + list(p.wh[1]) + [getattr(p, "phi_m_prev", None)] if roles else []):
             role = roles.get(id(fn))
-            if role is not None:
+            if role is None:
+                continue
+            if role[0] == "PHIM":
+                f.phi_m = fn.data_ptr()
+            else:
                 (f.k_i if role[0] == "KI" else f.k_e)[role[1]] = fn.data_ptr()
         for k, fn in enumerate(prog.aux_functions):
+            if fn is None:      # a normal component
+                continue
             t = fn.x.array
             if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.numel() != self.n_vertices:
                 raise ValueError(f"'{fn.name}' is not a nodal field of this problem's mesh on the device")
@@ -203,11 +212,11 @@ class VolumeFunctional:
 
     def close(self):
         """free the plans' device memory (also done when the functional or its problem's context goes away)"""
-        be, ids = getattr(self, "backend", None), getattr(self, "ids", [])
-        self.ids = []
+        be, plans = getattr(self, "backend", None), getattr(self, "plans", [])
+        self.plans = []
         if be is not None and getattr(be, "ctx", None):
-            for fid in ids:
-                be.lib.knp_functional_destroy(be.ctx, fid)
+            for plan in plans:
+                getattr(be.lib, self.ABI + "_destroy")(be.ctx, plan.id)
 
     def __del__(self):
         try:
@@ -216,38 +225,36 @@ class VolumeFunctional:
             pass
 
     def __call__(self, out=None):
-        """The integrals per tag, [n_tags, n_out] on the device; the constants are read anew.  Enqueued: no host copy, no
-        synchronisation.  ``out``: a contiguous float64 device tensor of that size (a row of a preallocated trace), else a new one."""
-        spec, be = self.spec, self.backend
-        if spec.sides and not self.ids:
+        """The integrals per row, [n_tags, n_out] on the device; the constants and the tensors' addresses are read anew.  Enqueued:
+        no host copy, no synchronisation.  ``out``: a contiguous float64 device tensor of that size (a row of a preallocated trace),
+        else a new one."""
+        be = self.backend
+        if self.n_plans and not self.plans:
             raise _lib.KnpError("the functional is closed")
         shape = (len(self.tags), self.n_out)
         if out is None:
             out = torch.empty(shape, dtype=torch.float64, device=be.device)
         if not (out.is_contiguous() and out.dtype == torch.float64 and out.is_cuda and out.numel() == shape[0] * shape[1]):
             raise ValueError(f"out must be a contiguous float64 device tensor of {shape[0]} x {shape[1]} entries")
-        row = 0
-        for sp, fid in zip(spec.sides, self.ids):
-            f = self._fields(sp.spec)
-            consts = sp.spec.constants()
+        for plan in self.plans:
+            f = self._fields(plan.spec)
+            consts = plan.spec.constants()
             if consts.size:
-                be.check(be.lib.knp_functional_set_constants(be.ctx, fid, consts.shape[0], consts.ctypes.data_as(_lib.f64p)))
-            be.check(be.lib.knp_functional_eval(be.ctx, fid, C.byref(f), C.c_void_p(out.data_ptr() + 8 * row * self.n_out)))
-            row += len(sp.tags)
+                be.check(getattr(be.lib, self.ABI + "_set_constants")(be.ctx, plan.id, consts.shape[0], consts.ctypes.data_as(_lib.f64p)))
+            be.check(getattr(be.lib, self.ABI + "_eval")(be.ctx, plan.id, C.byref(f), C.c_void_p(out.data_ptr() + 8 * plan.first * self.n_out)))
         return out.view(shape)
 
     def value(self):
-        """the integrals per tag as NumPy [n_tags, n_out] (one read-back)"""
+        """the integrals per row as NumPy [n_tags, n_out] (one read-back)"""
         return self().cpu().numpy()
 
     def total(self):
-        """the sum over the tags, [n_out]"""
+        """the sum over the rows, [n_out]"""
         return self.value().sum(axis=0)
 
 
-def assemble_scalar(problem, integrand_i=None, integrand_e=None, tags=None, degree=2):
-    """what ``ProblemKNPEMI.assemble_scalar`` and ``ProblemEMI.assemble_scalar`` do: one functional, one evaluation, the sum over tags"""
-    F = VolumeFunctional(problem, integrand_i, integrand_e, tags, degree)
+def _total_once(F):
+    """one evaluation of a new functional, the sum over its rows: a float where the integrand was one expression"""
     try:
         tot = F.total()
     finally:
@@ -255,10 +262,29 @@ def assemble_scalar(problem, integrand_i=None, integrand_e=None, tags=None, degr
     return float(tot[0]) if F.spec.single else tot
 
 
+class VolumeFunctional(_Functional):
+    """Per cell tag, the integral of ``integrand_i`` (intracellular tags) or ``integrand_e`` (extracellular tags) with a rule exact to
+    polynomial ``degree``.  Each integrand is one expression or a list of up to three (both sides the same number); ``tags``: None
+    for every cell tag of the sides that have an integrand.  ``tags`` / ``side`` / ``volume``: per row of the result -- the
+    intracellular tags first, each side's in the order given.  A call returns the device tensor [n_tags, n_out]."""
+    ABI, ITEMS = "knp_functional", "cells"
+    FEATURE = FEATURE
+    roles = staticmethod(field_roles)
+
+    def __init__(self, problem, integrand_i=None, integrand_e=None, tags=None, degree=2):
+        spec = self.spec = compile_functional(problem, integrand_i, integrand_e, tags, degree)
+        self.tags, self.side, self.volume, self.n_out, self.degree = spec.tags, spec.side, spec.volume, spec.n_out, spec.degree
+        self._open(problem)
+        for sp in spec.sides:
+            self._create(sp.spec, len(sp.tags), sp.seg_ptr, sp.cells, spec.q_bary, spec.q_w)
+
+
+def assemble_scalar(problem, integrand_i=None, integrand_e=None, tags=None, degree=2):
+    """what ``ProblemKNPEMI.assemble_scalar`` and ``ProblemEMI.assemble_scalar`` do: one functional, one evaluation, the sum over tags"""
+    return _total_once(VolumeFunctional(problem, integrand_i, integrand_e, tags, degree))
+
+
 # ------------------------------------------------------------------------------------------ membrane functionals
-MEMBRANE_FEATURE = "membrane functionals (MembraneFunctional / assemble_scalar_membrane / add_functional)"
-
-
 def membrane_field_roles(problem):
     """``field_roles`` and, on a KNP-EMI problem, ``phi_m_prev`` as ``PHIM``: the roles of the membrane programs"""
     roles = field_roles(problem)
@@ -317,7 +343,7 @@ def compile_membrane_functional(problem, integrand, tags=None, degree=10):
     return spec
 
 
-class MembraneFunctional:
+class MembraneFunctional(_Functional):
     """Per membrane tag, the integral of ``integrand`` over that tag's facets with a facet rule exact to polynomial ``degree`` (10:
     the problem's own ``q_pts``).  The integrand is one expression or a list of up to three; besides what a volume functional
     takes it may hold ``fem.grad(f)[a]('+' | '-')``, ``fem.FacetNormal(mesh)[a]('+' | '-')``, ``fem.NormalDerivative(f, side)`` and
@@ -325,98 +351,17 @@ class MembraneFunctional:
     ``problem.gamma_tags``, each on its own, or a list whose entries are tags or tuples of tags pooled into one row.  ``groups`` /
     ``tags`` (each row's first tag) / ``area``: per row of the result.  A call returns the device tensor [n_tags, n_out]."""
 
+    ABI, ITEMS = "knp_membrane_functional", "facets"
+    FEATURE = MEMBRANE_FEATURE
+    roles = staticmethod(membrane_field_roles)
+
     def __init__(self, problem, integrand, tags=None, degree=10):
-        self.problem = problem
-        self.id = None
         spec = self.spec = compile_membrane_functional(problem, integrand, tags, degree)
         self.tags, self.groups, self.area, self.n_out, self.degree = spec.tags, spec.groups, spec.area, spec.n_out, spec.degree
-        if problem.comm.size > 1:
-            raise NotImplementedError(f"{MEMBRANE_FEATURE} run on one rank: a functional integrates this rank's owned facets only and "
-                                      "the sum over ranks is not implemented")
-        be = self.backend = _backend(problem)
-        self.n_vertices = problem.local_mesh.coords.shape[0]
-        i32, f64 = (lambda a: a.ctypes.data_as(_lib.i32p)), (lambda a: a.ctypes.data_as(_lib.f64p))
-        prog = spec.spec
-        code = np.ascontiguousarray(prog.code, dtype=np.int32)
-        consts = prog.constants()
-        modes = np.ascontiguousarray(prog.aux_derivs, dtype=np.int32)
-        fid = C.c_int32(-1)
-        be.check(be.lib.knp_membrane_functional_create(be.ctx, len(spec.tags), i32(spec.seg_ptr), i32(spec.facets) if spec.facets.size else None,
-                                                       len(spec.q_w), f64(spec.q_pts), f64(spec.q_w), code.shape[0], i32(code), consts.shape[0],
-                                                       f64(consts) if consts.size else None, modes.shape[0], i32(modes) if modes.size else None,
-                                                       spec.n_out, C.byref(fid)))
-        self.id = int(fid.value)
-        self._fields()      # refuses a Function that is not a nodal field of this mesh now, not at the first call
-
-    def _fields(self):
-        """the ABI's struct of device pointers, filled at every call: a Function whose ``x.array`` was bound to another tensor in
-        between is read where it is now"""
-        p = self.problem
-        f = _lib.Fields()
-        roles = membrane_field_roles(p)
-        if roles:
-            for fn in list(p.wh[0]) + list(p.wh[1]) + [p.phi_m_prev]:
-                role = roles.get(id(fn))
-                if role is None:
-                    continue
-                if role[0] == "PHIM":
-                    f.phi_m = fn.data_ptr()
-                else:
-                    (f.k_i if role[0] == "KI" else f.k_e)[role[1]] = fn.data_ptr()
-        for k, fn in enumerate(self.spec.spec.aux_functions):
-            if fn is None:      # a normal component
-                continue
-            t = fn.x.array
-            if t.dtype != torch.float64 or not t.is_cuda or not t.is_contiguous() or t.numel() != self.n_vertices:
-                raise ValueError(f"'{fn.name}' is not a nodal field of this problem's mesh on the device")
-            f.aux[k] = fn.data_ptr()
-        return f
-
-    def close(self):
-        """free the plan's device memory (also done when the functional or its problem's context goes away)"""
-        be, fid = getattr(self, "backend", None), getattr(self, "id", None)
-        self.id = None
-        if fid is not None and be is not None and getattr(be, "ctx", None):
-            be.lib.knp_membrane_functional_destroy(be.ctx, fid)
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:      # noqa: BLE001
-            pass
-
-    def __call__(self, out=None):
-        """The integrals per row, [n_tags, n_out] on the device; the constants and the tensors' addresses are read anew.  Enqueued:
-        no host copy, no synchronisation.  ``out``: a contiguous float64 device tensor of that size, else a new one."""
-        be = self.backend
-        if self.id is None:
-            raise _lib.KnpError("the functional is closed")
-        shape = (len(self.tags), self.n_out)
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float64, device=be.device)
-        if not (out.is_contiguous() and out.dtype == torch.float64 and out.is_cuda and out.numel() == shape[0] * shape[1]):
-            raise ValueError(f"out must be a contiguous float64 device tensor of {shape[0]} x {shape[1]} entries")
-        f = self._fields()
-        consts = self.spec.spec.constants()
-        if consts.size:
-            be.check(be.lib.knp_membrane_functional_set_constants(be.ctx, self.id, consts.shape[0], consts.ctypes.data_as(_lib.f64p)))
-        be.check(be.lib.knp_membrane_functional_eval(be.ctx, self.id, C.byref(f), C.c_void_p(out.data_ptr())))
-        return out.view(shape)
-
-    def value(self):
-        """the integrals per row as NumPy [n_tags, n_out] (one read-back)"""
-        return self().cpu().numpy()
-
-    def total(self):
-        """the sum over the rows, [n_out]"""
-        return self.value().sum(axis=0)
+        self._open(problem)
+        self._create(spec.spec, len(spec.tags), spec.seg_ptr, spec.facets, spec.q_pts, spec.q_w)
 
 
 def assemble_scalar_membrane(problem, integrand, tags=None, degree=10):
     """what ``assemble_scalar_membrane`` of both problem classes does: one functional, one evaluation, the sum over the rows"""
-    F = MembraneFunctional(problem, integrand, tags, degree)
-    try:
-        tot = F.total()
-    finally:
-        F.close()
-    return float(tot[0]) if F.spec.single else tot
+    return _total_once(MembraneFunctional(problem, integrand, tags, degree))

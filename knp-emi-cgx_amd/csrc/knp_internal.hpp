@@ -65,7 +65,6 @@ void knp_emi_free(knp_ctx* ctx);
 void knp_state_free(knp_ctx* ctx);
 void knp_sample_free(knp_ctx* ctx);
 void knp_functional_free(knp_ctx* ctx);
-void knp_membrane_functional_free(knp_ctx* ctx);
 
 // ---- the EMI model (knp_emi.inc): one unknown per node on the graph knp_create built ------------------------------------------
 struct KnpEmi {
@@ -124,29 +123,17 @@ struct KnpSamplePlan {
     std::vector<double> h_w;       // [n*(dim+1)] weights, caller's order
 };
 
-// ---- volume functional (knp_functional.inc): tag map of cells, quadrature rule and program of one knp_functional_create ---------------
+// ---- functional (knp_functional.inc, knp_membrane_functional.inc): tag map, quadrature rule and program of one create of either kind ---
 struct KnpFunctional {
     bool live = false;
     int n_q = 0, n_out = 0, n_instr = 0, n_regs = 0, n_consts = 0;
-    unsigned need = 0;             // the field slots the code reads (FN_* bits)
-    int8_t aux_deriv[KNP_MAX_AUX] = {-1, -1, -1, -1, -1, -1, -1, -1};   // per aux slot: -1 value, a = d/dx_a
-    KnpDiagMap map;                // owned cells sorted by dense tag index, chunks of 128
+    unsigned need = 0;             // the field slots the code reads (FN_* bits) and, on a membrane plan, the cells whose geometry it needs
+    int8_t aux_mode[KNP_MAX_AUX] = {-1, -1, -1, -1, -1, -1, -1, -1};   // per aux slot: -1 value, 0..2 d/dx_a; a membrane plan also 3..5
+                                   // d/dx_a on the '-' cell, 6 / 7 d/dn, 8.. normal component
+    KnpDiagMap map;                // owned cells, or membrane facets (indices into the Gamma list), sorted by dense tag index, chunks of 128
     int32_t* d_code = nullptr;     // [n_instr*4]
-    double* d_qb = nullptr;        // [n_q*(dim+1)] barycentric points
-    double* d_qw = nullptr;        // [n_q] weights, sum 1
-    double consts[KNP_DIAG_MAX_CONSTS] = {};   // host copy: passed to the kernel by value at every launch
-};
-
-// ---- membrane functional (knp_membrane_functional.inc): facet map, facet rule, program and per-facet records of one create ------------
-struct KnpMembraneFunctional {
-    bool live = false;
-    int n_q = 0, n_out = 0, n_instr = 0, n_regs = 0, n_consts = 0;
-    unsigned need = 0;             // the field slots the code reads (FN_* bits) and the cells whose geometry it needs (MF_GEOM_*)
-    int8_t aux_mode[KNP_MAX_AUX] = {-1, -1, -1, -1, -1, -1, -1, -1};   // per aux slot: -1 value, 0..5 d/dx_a (+ / - cell), 6 / 7 d/dn, 8.. normal
-    KnpDiagMap map;                // membrane facets (indices into the Gamma list) sorted by dense tag index, chunks of 128
-    int32_t* d_code = nullptr;     // [n_instr*4]
-    int32_t* d_rec = nullptr;      // [map.n*8] per facet in map order: 2 x (facet vertices, opposite vertex), 16-byte units
-    double* d_qp = nullptr;        // [n_q*dim] barycentric points on the facet
+    int32_t* d_rec = nullptr;      // membrane plan: [map.n*8] per facet in map order, 2 x (facet vertices, opposite vertex); else null
+    double* d_qp = nullptr;        // [n_q*(dim+1)] barycentric points of the cell rule, or [n_q*dim] of the facet rule
     double* d_qw = nullptr;        // [n_q] weights, sum 1
     double consts[KNP_DIAG_MAX_CONSTS] = {};   // host copy: passed to the kernel by value at every launch
 };
@@ -487,7 +474,7 @@ struct knp_ctx {
     KnpStates states;
     std::vector<KnpSamplePlan> sample_plans;   // knp_sample_plan_create: the id is the index; a destroyed slot is reused
     std::vector<KnpFunctional> functionals;    // knp_functional_create: likewise
-    std::vector<KnpMembraneFunctional> membrane_functionals;   // knp_membrane_functional_create: likewise
+    std::vector<KnpFunctional> membrane_functionals;   // knp_membrane_functional_create: likewise
     // profiling
     int prof_on = 0;
     std::vector<hipEvent_t> prof_pool;   // recycled timing events

@@ -3102,7 +3102,6 @@ int knp_destroy(knp_ctx* ctx) {
     knp_state_free(ctx);
     knp_sample_free(ctx);
     knp_functional_free(ctx);
-    knp_membrane_functional_free(ctx);
     delete ctx;
     return KNP_OK;
 }

@@ -1,6 +1,7 @@
 """Membrane functionals on the device (csrc/knp_membrane_functional.inc, cgx_hip/functionals.py): closed forms, the hard-wired
 membrane reductions on the same fields, integrands against the NumPy reference (tests/membrane_functional_ref.py), a pooled row longer
-than the wave combine, every error of the raw ABI, a flat adjacent cell, the EMI model and a run that records functionals.
+than the wave combine, every error of the raw ABI, a flat adjacent cell, every instantiation of the two kinds' kernels, the two kinds'
+plan tables side by side, the EMI model and a run that records functionals.
 
 Tolerance throughout: |device - host| <= 1e-12 * sum |w f| per row and output (``functional_ref.TOL``), the bound of the volume
 functionals: the same interpreter, the same reduction."""
@@ -14,6 +15,7 @@ import functional_ref
 import membrane_functional_ref as mref
 from functional_ref import TOL
 from parity_utils import ci_config, make_problem, tissue_config
+from test_gpu_functionals import _Raw as _RawVolume
 from test_gpu_functionals import _randomize
 
 pytestmark = pytest.mark.gpu
@@ -492,6 +494,94 @@ def test_an_extracellular_cell_that_does_not_hold_the_facet_is_a_mesh_error():
             assert rc == 0 and fid == k, (m, raw.error())
     finally:
         lib.knp_destroy(ctx)
+
+
+# ------------------------------------------------------------------------------------------ both kinds, every kernel
+def _facet_length(p):
+    return float(p._fmeas.mean()) ** (1.0 / (p.local_mesh.coords.shape[1] - 1))
+
+
+def _mixed_volume_forms(p, user, n_out):
+    """per side ``n_out`` outputs, each a concentration (KI / KE), a nonlinear term of the potential (an aux value) and a derivative
+    slot, the axis moving with the output"""
+    from cgx_hip import fem
+    dim, h = p.local_mesh.coords.shape[1], _facet_length(p)
+    return [[p.wh[s][j] + fem.exp(8.0 * p.wh[s][p.N_ions]) * fem.grad(user)[(j + 1) % dim] * h for j in range(n_out)] for s in range(2)]
+
+
+def _mixed_membrane_outs(p, user, n_out):
+    """``n_out`` outputs, each a concentration, a nonlinear term of the potential times a '+' gradient of the user's field, and a
+    '-' normal derivative"""
+    from cgx_hip import fem
+    dim, h = p.local_mesh.coords.shape[1], _facet_length(p)
+    return [p.wh[0][j] + fem.exp(8.0 * p.wh[0][p.N_ions]) * fem.grad(user)[(j + 1) % dim]("+") * h
+            + fem.sqrt(p.wh[1][j]) * fem.NormalDerivative(user, "-") * h for j in range(n_out)]
+
+
+@pytest.mark.parametrize("n_out", [1, 2, 3])
+@pytest.mark.parametrize("case", ["square", "cube"])
+def test_every_instantiation_of_both_kernels(problems, case, n_out):
+    """k_functional and k_membrane_functional over <2 | 3, 1 | 2 | 3>, each named here and not reached by the way"""
+    from cgx_hip.functionals import MembraneFunctional, VolumeFunctional
+    p, be, user = problems(case)
+    forms = _mixed_volume_forms(p, user, n_out)
+    V = VolumeFunctional(p, forms[0], forms[1], degree=2)
+    assert V.n_out == n_out and all(-1 in sp.spec.aux_derivs and max(sp.spec.aux_derivs) >= 0 for sp in V.spec.sides)
+    _, _, want, scale = functional_ref.reference(p, forms[0], forms[1], degree=2)
+    assert want.shape == (len(V.tags), n_out) and np.all(scale > 0)
+    _check(V.value(), want, scale, f"volume kernel <{p.local_mesh.coords.shape[1]}, {n_out}>")
+    outs = _mixed_membrane_outs(p, user, n_out)
+    M = MembraneFunctional(p, outs, degree=2)
+    modes = set(M.spec.spec.aux_derivs)
+    assert M.n_out == n_out and -1 in modes and 7 in modes and modes & {0, 1, 2}
+    _, want, scale = mref.reference(p, outs, degree=2)
+    assert want.shape == (len(M.tags), n_out) and np.all(scale > 0)
+    _check(M.value(), want, scale, f"membrane kernel <{p.local_mesh.coords.shape[1]}, {n_out}>")
+
+
+def test_two_plan_tables_one_lifecycle():
+    """The two kinds keep their plans apart: each kind's first plan has id 0, destroying one kind's plan leaves the other kind's plan
+    of the same id as it was, the destroyed id is unknown to its own kind only, and its slot is taken again."""
+    from cgx_hip import _lib
+    p = make_problem(ci_config(N=8, steps=1), "ci")
+    be = p.create_backend()
+    _randomize(p, 67)
+    lib, ctx = be.lib, be.ctx
+    kinds = {"volume": (_RawVolume(be, int(p.local_mesh.n_cells_owned), 2), lib.knp_functional_eval, lib.knp_functional_destroy,
+                        "unknown functional 0"),
+             "membrane": (_Raw(be, len(p._fv), 2), lib.knp_membrane_functional_eval, lib.knp_membrane_functional_destroy,
+                          "unknown membrane functional 0")}
+    f = _lib.Fields()
+    f.aux[0] = p.wh[0][3].data_ptr()
+    sentinel = -123.25
+
+    def evaluate(kind):
+        out = torch.full((1,), sentinel, dtype=torch.float64, device=be.device)
+        rc = kinds[kind][1](ctx, 0, C.byref(f), C.c_void_p(out.data_ptr()))
+        torch.cuda.synchronize()
+        return rc, out.cpu().numpy()
+
+    for gone, stays in (("volume", "membrane"), ("membrane", "volume")):
+        for kind in (gone, stays):
+            rc, fid = kinds[kind][0].create()
+            assert rc == 0 and fid == 0, (kind, kinds[kind][0].error())
+        before = {}
+        for kind in (gone, stays):
+            rc, before[kind] = evaluate(kind)
+            assert rc == 0 and before[kind][0] != sentinel and np.isfinite(before[kind][0]), (kind, kinds[kind][0].error())
+        assert before["volume"][0] != before["membrane"][0]
+        raw, _, destroy, unknown = kinds[gone]
+        assert destroy(ctx, 0) == 0, raw.error()
+        rc, after = evaluate(stays)
+        assert rc == 0 and after.tobytes() == before[stays].tobytes(), (stays, kinds[stays][0].error())
+        rc, untouched = evaluate(gone)
+        assert rc == -1 and raw.error() == unknown and untouched[0] == sentinel      # nothing was launched
+        rc, fid = raw.create()
+        assert rc == 0 and fid == 0, raw.error()
+        rc, again = evaluate(gone)
+        assert rc == 0 and again.tobytes() == before[gone].tobytes()
+        for kind in (gone, stays):
+            assert kinds[kind][2](ctx, 0) == 0, kinds[kind][0].error()
 
 
 # ------------------------------------------------------------------------------------------ EMI and whole runs
