@@ -471,18 +471,35 @@ def cpu_share() -> int:
     return max(1, min(n, 32))
 
 
-def dense_pseudo_inverse(A: sp.spmatrix) -> np.ndarray:
+def dense_pseudo_inverse(A: sp.spmatrix, null_dim: int = 0) -> np.ndarray:
     """Pseudo-inverse of the coarsest operator (the potential blocks are singular up to the membrane term).  The
     Galerkin operators of the symmetric blocks of P are symmetric: the eigenvalue route is 3-4x cheaper than the SVD,
-    which used to be half of the whole host setup; operators with Dirichlet (identity) rows take the general route."""
+    which used to be half of the whole host setup; operators with Dirichlet (identity) rows take the general route.
+
+    ``null_dim``: the fine operator is KNOWN to be singular with a null space of that dimension (pure Neumann EMI: the constant).
+    Its coarse image is then a null vector of the Galerkin operator only as far as the prolongators reproduce it: where an unknown
+    is split off without an aggregate they do not, and the mode arrives with a small positive eigenvalue (5.9e-12 against 1.3e-3
+    on a 24-row coarse level) that no relative cut-off tells from the smallest physical one (1.4e-8, the per-side constants held
+    together by the membrane).  Inverted, it puts a nearly constant component 1e11 times the rest into every preconditioned
+    residual, and the projection of the solver loses that many digits.  So the ``null_dim`` modes of smallest |eigenvalue| are
+    left out of the inverse whatever their size (symmetric operators only); the smoother alone acts on them."""
     D = A.toarray()
     sym = np.abs(D - D.T).max() <= 1e-12 * max(np.abs(D).max(), 1e-300)
+
+    def inverse():
+        if null_dim > 0 and sym and D.shape[0] > null_dim:
+            w, V = np.linalg.eigh(D)
+            order = np.argsort(np.abs(w))
+            keep = order[null_dim:]
+            keep = keep[np.abs(w[keep]) > 1e-13 * np.abs(w).max()]
+            return (V[:, keep] / w[keep]) @ V[:, keep].T
+        return np.linalg.pinv(D, rcond=1e-13, hermitian=bool(sym))
     try:        # LAPACK on the CPU share of the process, not on every logical CPU of the host
         from threadpoolctl import threadpool_limits
         with threadpool_limits(limits=cpu_share()):
-            return np.linalg.pinv(D, rcond=1e-13, hermitian=bool(sym))
+            return inverse()
     except ImportError:
-        return np.linalg.pinv(D, rcond=1e-13, hermitian=bool(sym))
+        return inverse()
 
 
 def upload(lib, ctx, check, hier: Hierarchy, pre: int = 1, post: int = 1, cheby_degree: int = 2, index: int = 0, level0_native: bool = False):

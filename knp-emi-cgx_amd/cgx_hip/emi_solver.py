@@ -19,6 +19,22 @@ from . import _lib, amg
 from .emi_problem import ProblemEMI
 
 
+def build_emi_hierarchy(A, pure_neumann, theta, coarse_size, smoother_degree, setup="host", device=None):
+    """Aggregation hierarchy on the EMI matrix for the generic level-by-level cycle (A, P, R per level and the dense coarse inverse).
+    ``pure_neumann``: A 1 = 0, so one coarse mode is the image of the constant; it is left out of the coarse inverse whatever
+    eigenvalue the transfer operators gave it (``amg.dense_pseudo_inverse``)."""
+    if setup == "gpu":
+        from . import amg_gpu
+        h = amg_gpu.build_hierarchy(A, theta=theta, coarse_size=coarse_size, device=device, smoother_degree=smoother_degree)
+    else:
+        h = amg.build_hierarchy(A, theta=theta, coarse_size=coarse_size, smoother_degree=smoother_degree)
+    for lv in h.levels:
+        lv.S = lv.Rt = lv.U = None
+    if pure_neumann and h.coarse_inv is not None:
+        h.coarse_inv = np.ascontiguousarray(amg.dense_pseudo_inverse(h.levels[-1].A, null_dim=1))
+    return h
+
+
 class SolverEMI:
     # ---- default iterative solver parameters (EMIx_solver.py:543-561)
     ksp_rtol = 1e-6
@@ -105,15 +121,8 @@ class SolverEMI:
         A = getattr(p, "P", None)
         if A is None:
             A = p.setup_preconditioner()
-        if self.amg_setup == "gpu":
-            from . import amg_gpu
-            h = amg_gpu.build_hierarchy(A, theta=self.amg_theta, coarse_size=self.amg_coarse_size, device=self.backend.device,
-                                        smoother_degree=self.amg_cheby_degree)
-        else:
-            h = amg.build_hierarchy(A, theta=self.amg_theta, coarse_size=self.amg_coarse_size, smoother_degree=self.amg_cheby_degree)
-        for lv in h.levels:        # the generic level-by-level cycle needs A, P, R only
-            lv.S = lv.Rt = lv.U = None
-        return h
+        neumann = not (p.dirichlet_bcs and len(p.bc_vertices)) and not len(getattr(self.backend, "bc_nodes", ()))
+        return build_emi_hierarchy(A, neumann, self.amg_theta, self.amg_coarse_size, self.amg_cheby_degree, self.amg_setup, self.backend.device)
 
     def setup_solver(self):
         be = self.backend

@@ -142,6 +142,9 @@ class EmiRef:
         self.A.sum_duplicates()
         self.A.sort_indices()
         self.absA_gamma = abs(G_)
+        # sum of the magnitudes of the cell and facet terms behind each entry of A: an entry whose terms cancel is known to eps of this
+        absKs = sp.csr_matrix((np.abs(sig[:, None, None] * Kc).ravel(), (r, c)), shape=(self.n, self.n))
+        self.absA_terms = (self.dt * absKs + self.absA_gamma).tocsr()
         self.q_pts, self.q_w = facet_quadrature(d, degree)
         self.facet_model = np.zeros(len(self.fv), dtype=np.int64) if facet_model is None else np.asarray(facet_model, dtype=np.int64)
         self.models = [passive_current]
@@ -232,6 +235,62 @@ class EmiRef:
             one = sp.csr_matrix(np.ones((self.n, 1)))
             self._lu = spla.splu(sp.bmat([[self.A, one], [one.T, None]]).tocsc())
         return self._lu.solve(np.concatenate([b, [0.0]]))[:self.n]
+
+    # ---- k steps of preconditioned conjugate gradients
+    def pcg(self, b, k, pc="none", norm_type="preconditioned", x0=None, dtype=np.float64):
+        """Exactly ``k`` iterations of the recurrence that ``knp_emi_cg_solve`` documents (include/knpemi_hip.h; PETSc's KSPCG with a
+        projected preconditioner), on ``self.operator()``, in ``dtype`` (``np.longdouble`` for the reference's own rounding spread):
+
+            x = x0 (b on the Dirichlet nodes);  r = b - A x, its mean removed once when the null space is on
+            z = B r;  z' = z - mean(z) (null space on);  beta = r . z';  p = z'
+            k times:  alpha = beta / (p . A p);  x += alpha p;  r -= alpha A p;  z, z', beta_new as above;  p = z' + (beta_new / beta) p
+
+        ``pc``: "none" (B = I) or "jacobi" (B = 1 / diag A; 1 on Dirichlet nodes).  Norms: preconditioned ||z'||_2, unpreconditioned
+        ||r||_2, natural sqrt|r . z'|.  Returns x, r and the k + 1 norms (before the first iteration, then after each).  Sums are
+        NumPy's own (pairwise): nothing of the kernels' block order is restated."""
+        A = self.operator().tocsr()
+        A.sort_indices()
+        T = np.dtype(dtype).type
+        n = self.n
+        ns = self.nullspace and len(self.bc_nodes) == 0
+        data, indices, starts = A.data.astype(T), A.indices, A.indptr[:-1]
+        assert np.all(np.diff(A.indptr) > 0)                       # every row holds its diagonal: reduceat sees no empty segment
+        mul = (lambda v: A @ v) if T is np.float64 else (lambda v: np.add.reduceat(data * v[indices], starts))
+        if pc == "jacobi":
+            d = A.diagonal().astype(T)
+            d[self.bc_nodes] = 1
+            B = lambda v: v / d
+        elif pc == "none":
+            B = lambda v: v.copy()
+        else:
+            raise ValueError(pc)
+        b = np.asarray(b).astype(T)
+        x = np.zeros(n, dtype=T) if x0 is None else np.asarray(x0).astype(T)
+        x[self.bc_nodes] = b[self.bc_nodes]
+        r = b - mul(x)
+        if ns:
+            r = r - r.sum() / T(n)
+
+        def apply(r):
+            z = B(r)
+            if ns:
+                z = z - z.sum() / T(n)
+            beta = r @ z
+            norm = {"preconditioned": np.sqrt(z @ z), "unpreconditioned": np.sqrt(r @ r), "natural": np.sqrt(abs(beta))}[norm_type]
+            return z, beta, norm
+        z, beta, norm = apply(r)
+        p = z.copy()
+        norms = [norm]
+        for _ in range(k):
+            q = mul(p)
+            alpha = beta / (p @ q)
+            x = x + alpha * p
+            r = r - alpha * q
+            z, beta_new, norm = apply(r)
+            p = z + (beta_new / beta) * p
+            beta = beta_new
+            norms.append(norm)
+        return x, r, np.array(norms, dtype=T)
 
     def split(self, x):
         """nodal phi_i, phi_e (0 where a vertex has no node of that side) and phi_M = phi_i - phi_e"""

@@ -141,13 +141,23 @@ def check_launch(info, name):
     assert (info["asm_stage"] > 0) == (e["asm_variant"] > 0), (name, info)
     assert info["asm_group"] == e["asm_group"] and info["spmv_group"] == info["pc_group"] == e["asm_group"] // 2, (name, info)
     assert -(-info["max_node_pairs"] // info["asm_group"]) == e["trips"], (name, info)
+
+
+# Meshes for the EMI kernels (csrc/knp_emi.inc; DESIGN.md section 4, "Irregular meshes"): a 3D hub ON the membrane, and two plain 2D
+# meshes sized by the fixed grids of the EMI solver's kernels.  Kept apart from MESHES: the KNP-EMI parametrisations do not change.
+MEMBRANE_HUB_3D = (0.25, 0.5, 0.5)
+EMI_MESHES = {
+    "hub3d_5_60m": lambda: hub3d(5, 60, centre=MEMBRANE_HUB_3D),
+    "delaunay2d_92": lambda: delaunay2d(92, seed=3),
+    "delaunay2d_365": lambda: delaunay2d(365, seed=3),
+}
 _CACHE = {}
 
 
 def mesh(name):
     """the mesh of that name, generated once per process; callers must not write into the arrays"""
     if name not in _CACHE:
-        m = MESHES[name]()
+        m = (MESHES[name] if name in MESHES else EMI_MESHES[name])()
         for a in m:
             a.setflags(write=False)
         _CACHE[name] = m
@@ -159,6 +169,31 @@ def two_tag(coords, cells, tags):
     tag 1; membrane facets take the tag of their intracellular cell (``"intra"``, the convention of the tissue configs)."""
     cx = coords[cells].mean(axis=1)[:, 0]
     return np.where(tags == 1, np.where(cx < 0.5, 2, 3), 1).astype(np.int32)
+
+
+def emi_arrays(name, two=False):
+    """What ``ProblemEMI`` makes of the named mesh at ``mesh_conversion_factor`` 1e-6: ``(coords, cells, cell_tags, intra_tags,
+    extra_tags, gamma, gamma_tags, facet_vertices)``.  ``two``: the ``two_tag`` split, membrane tag = tag of the intracellular cell
+    (2 or 3); else one cell (tag 1 in 2) whose membrane carries the default tag 4."""
+    from cgx_hip import mesh as meshmod
+    coords, cells, tags = mesh(name)
+    if two:
+        tags, intra, extra, how = two_tag(coords, cells, tags), (2, 3), (1,), "intra"
+    else:
+        intra, extra, how = (1,), (2,), None
+    gamma, gtags, fverts = meshmod.gamma_integration_entities(cells, tags, intra, extra, how)
+    return coords * 1e-6, cells, tags, intra, extra, gamma, gtags, fverts
+
+
+def emi_config(tmp_path, name, two=False):
+    """config keys that put the named mesh (``tmp_path/<name>[_two_tag].npz``) under a ``ProblemEMI``: the arrays of ``emi_arrays``"""
+    coords, cells, tags = mesh(name)
+    if not two:
+        path = write_npz(tmp_path, name, coords, cells, tags)
+        return {"cell_tag_file": path, "facet_tag_file": path, "input_dir": "", "ics_tags": [1], "ecs_tags": [2], "membrane_tags": [4]}
+    _, _, t2, _, _, _, gtags, fverts = emi_arrays(name, True)
+    path = write_npz(tmp_path, name + "_two_tag", coords, cells, t2, fverts, gtags)
+    return {"cell_tag_file": path, "facet_tag_file": path, "input_dir": "", "ics_tags": [2, 3], "ecs_tags": [1], "membrane_tags": [2, 3]}
 
 
 def write_npz(tmp_path, name, coords, cells, tags, facets=None, facet_tags=None):
