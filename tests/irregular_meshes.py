@@ -151,13 +151,32 @@ EMI_MESHES = {
     "delaunay2d_92": lambda: delaunay2d(92, seed=3),
     "delaunay2d_365": lambda: delaunay2d(365, seed=3),
 }
+
+
+def reoriented(name, seed):
+    """The named mesh with the vertex order inside every cell permuted by a seeded RNG: half the permutations are odd, so about half
+    the 2D cells come out clockwise (negative edge determinant; the Delaunay generators emit counter-clockwise triangles only).
+    Coordinates, tags, the vertex numbering and the order of the cells are the parent's, so the node graph is the parent's."""
+    coords, cells, tags = mesh(name)
+    rng = np.random.default_rng(seed)
+    order = rng.permuted(np.tile(np.arange(cells.shape[1]), (cells.shape[0], 1)), axis=1)
+    return coords, np.ascontiguousarray(np.take_along_axis(cells, order, axis=1)), tags
+
+
+# Reoriented twins for the functional kernels and the det < 0 branch of every 2D kernel (DESIGN.md section 4, "Irregular meshes"); the
+# launch expectations of a twin are its parent's (EXPECT[PARENT[name]]): the graph is identical.
+ORIENTED = {
+    "delaunay2d_12_cw": lambda: reoriented("delaunay2d_12", seed=5),
+    "hub2d_12_48m_cw": lambda: reoriented("hub2d_12_48m", seed=7),
+}
+PARENT = {"delaunay2d_12_cw": "delaunay2d_12", "hub2d_12_48m_cw": "hub2d_12_48m"}
 _CACHE = {}
 
 
 def mesh(name):
     """the mesh of that name, generated once per process; callers must not write into the arrays"""
     if name not in _CACHE:
-        m = (MESHES[name] if name in MESHES else EMI_MESHES[name])()
+        m = next(d for d in (MESHES, EMI_MESHES, ORIENTED) if name in d)[name]()
         for a in m:
             a.setflags(write=False)
         _CACHE[name] = m

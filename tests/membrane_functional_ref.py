@@ -6,7 +6,7 @@ import math
 
 import numpy as np
 
-from functional_ref import TOL, functions_of as _volume_functions_of, simplex_gradients  # noqa: F401  (TOL is re-exported)
+from functional_ref import TOL, functions_of as _volume_functions_of, geometry_longdouble, simplex_gradients  # noqa: F401  (TOL is re-exported)
 
 
 def functions_of(e, found=None):
@@ -34,9 +34,22 @@ def opposite_vertices(cells, gamma, fv):
     return opp
 
 
-def integrate_facets(coords, fv, opp, meas, exprs, qp, qw, sides=None):
+def facet_measures_longdouble(coords, fv):
+    """|F| of the facets ``fv`` [n, d] from their coordinates in ``np.longdouble`` (edge length / triangle area), rounded to fp64 once"""
+    X = np.asarray(coords[fv], dtype=np.longdouble)
+    e = X[:, 1:, :] - X[:, :1, :]
+    if fv.shape[1] == 2:
+        return np.sqrt((e[:, 0] ** 2).sum(axis=1)).astype(np.float64)
+    u, w = e[:, 0], e[:, 1]
+    c = np.stack([u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2], u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]], axis=1)
+    return (np.sqrt((c ** 2).sum(axis=1)) / 2).astype(np.float64)
+
+
+def integrate_facets(coords, fv, opp, meas, exprs, qp, qw, sides=None, longdouble=False):
     """per expression: (sum, sum of absolute values) of |F| q_w f over the facets ``fv`` [n, d] with the opposite vertices ``opp``
-    [n, 2] and the measures ``meas``.  ``sides``: {id(Function): 0 | 1}, the side an unrestricted derivative is taken on."""
+    [n, 2] and the measures ``meas``.  ``sides``: {id(Function): 0 | 1}, the side an unrestricted derivative is taken on.
+    ``longdouble``: the measures (``meas`` is not read), the gradients of the two cells and the normal are computed in
+    ``np.longdouble`` (``functional_ref.geometry_longdouble``) and rounded to fp64 once; everything else stays as it is."""
     from cgx_hip import fem
     sides = sides or {}
     n, d = fv.shape
@@ -48,11 +61,16 @@ def integrate_facets(coords, fv, opp, meas, exprs, qp, qw, sides=None):
         ok = n > 0 and np.all(opp[:, s] >= 0)
         cv = np.concatenate([fv, opp[:, s:s + 1]], axis=1) if ok else None
         cellv.append(cv)
-        G.append(simplex_gradients(coords[cv]) if ok else None)
+        G.append(simplex_gradients(coords[cv], longdouble) if ok else None)
     nrm = None
-    if G[0] is not None:
+    if G[0] is not None and longdouble:
+        g = geometry_longdouble(coords[cellv[0]])[0][:, d, :]
+        nrm = (-g / np.sqrt((g * g).sum(axis=1))[:, None]).astype(np.float64)
+    elif G[0] is not None:
         g = G[0][:, d, :]
         nrm = -g / np.linalg.norm(g, axis=1)[:, None]
+    if longdouble and n > 0:
+        meas = facet_measures_longdouble(coords, fv)
     fields, grads, nds = {}, {}, {}
     for e in exprs:
         for f in functions_of(e):
@@ -88,7 +106,7 @@ def default_sides(p):
     return {id(f): s for s in range(2) for f in wh[s]}
 
 
-def reference(problem, integrand, tags=None, degree=10):
+def reference(problem, integrand, tags=None, degree=10, longdouble=False):
     """(tags [rows], value [rows, n_out], scale [rows, n_out]): rows as ``MembraneFunctional`` orders them (``tags`` None: every tag of
     ``gamma_tags`` on its own; an entry may be a tuple of tags pooled into one row)"""
     from cgx_hip.diagnostics import facet_group_map
@@ -107,7 +125,7 @@ def reference(problem, integrand, tags=None, degree=10):
     val, scale = [], []
     for t in range(len(groups)):
         sel = facets[seg_ptr[t]:seg_ptr[t + 1]]
-        r = integrate_facets(lm.coords, fv[sel], opp[sel], p._fmeas[sel], exprs, qp, qw, sides)
+        r = integrate_facets(lm.coords, fv[sel], opp[sel], p._fmeas[sel], exprs, qp, qw, sides, longdouble)
         val.append([a for a, _ in r])
         scale.append([b for _, b in r])
     return np.array([g[0] for g in groups]), np.array(val), np.array(scale)

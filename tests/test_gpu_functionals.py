@@ -11,6 +11,8 @@ import pytest
 import torch
 
 import functional_ref
+from functional_raw import RawVolume as _Raw
+from functional_raw import _f64, _i32
 from functional_ref import TOL
 from parity_utils import ci_config, make_problem, tissue_config
 
@@ -214,39 +216,6 @@ def test_a_tag_of_more_than_64_chunks(long_tags):
 
 
 # ------------------------------------------------------------------------------------------ the raw ABI
-def _i32(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
-
-
-def _f64(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-class _Raw:
-    """knp_functional_create with valid default arguments (phi^2 of aux 0 over all owned cells as one tag), any of them replaced"""
-
-    def __init__(self, be, n_cells, dim):
-        from cgx_hip._lib import OPS
-        from cgx_hip.functionals import quadrature
-        self.be, self.dim = be, dim
-        qb, qw = quadrature(dim, 2)
-        self.args = dict(n_tags=1, seg_ptr=np.array([0, n_cells], dtype=np.int32), cells=np.arange(n_cells, dtype=np.int32),
-                         n_q=len(qw), q_bary=qb, q_w=qw, n_instr=3,
-                         code=np.array([[OPS["AUX"], 0, 0, 0], [OPS["MUL"], 1, 0, 0], [OPS["OUT"], 0, 0, 1]], dtype=np.int32),
-                         n_consts=0, consts=None, n_aux=1, aux_deriv=np.array([-1], dtype=np.int32), n_out=1, id=True)
-
-    def create(self, **kw):
-        a = dict(self.args, **kw)
-        fid = C.c_int32(-1)
-        rc = self.be.lib.knp_functional_create(self.be.ctx, a["n_tags"], _i32(a["seg_ptr"]), _i32(a["cells"]), a["n_q"], _f64(a["q_bary"]),
-                                               _f64(a["q_w"]), a["n_instr"], _i32(a["code"]), a["n_consts"], _f64(a["consts"]), a["n_aux"],
-                                               _i32(a["aux_deriv"]), a["n_out"], C.byref(fid) if a["id"] else None)
-        return rc, int(fid.value)
-
-    def error(self):
-        return (self.be.lib.knp_last_error(self.be.ctx) or b"").decode()
-
-
 def test_every_error_of_the_raw_abi(problems):
     from cgx_hip import _lib
     from cgx_hip._lib import OPS

@@ -13,9 +13,11 @@ import torch
 
 import functional_ref
 import membrane_functional_ref as mref
+from functional_raw import RawMembrane as _Raw
+from functional_raw import RawVolume as _RawVolume
+from functional_raw import _f64, _i32
 from functional_ref import TOL
 from parity_utils import ci_config, make_problem, tissue_config
-from test_gpu_functionals import _Raw as _RawVolume
 from test_gpu_functionals import _randomize
 
 pytestmark = pytest.mark.gpu
@@ -284,40 +286,6 @@ def test_a_pooled_row_of_more_than_64_chunks(long_row):
 
 
 # ------------------------------------------------------------------------------------------ the raw ABI
-def _i32(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_int32))
-
-
-def _f64(a):
-    return None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
-
-
-class _Raw:
-    """knp_membrane_functional_create with valid default arguments (the square of aux 0 over all facets as one tag), any replaced"""
-
-    def __init__(self, be, n_facets, dim):
-        from cgx_hip._lib import OPS
-        from cgx_hip.mesh import facet_quadrature
-        self.be, self.dim = be, dim
-        qp, qw = facet_quadrature(dim, 2)
-        self.args = dict(n_tags=1, seg_ptr=np.array([0, n_facets], dtype=np.int32), facets=np.arange(n_facets, dtype=np.int32),
-                         n_q=len(qw), q_pts=np.ascontiguousarray(qp), q_w=np.ascontiguousarray(qw), n_instr=3,
-                         code=np.array([[OPS["AUX"], 0, 0, 0], [OPS["MUL"], 1, 0, 0], [OPS["OUT"], 0, 0, 1]], dtype=np.int32),
-                         n_consts=0, consts=None, n_aux=1, aux_mode=np.array([-1], dtype=np.int32), n_out=1, id=True)
-
-    def create(self, **kw):
-        a = dict(self.args, **kw)
-        fid = C.c_int32(-1)
-        rc = self.be.lib.knp_membrane_functional_create(self.be.ctx, a["n_tags"], _i32(a["seg_ptr"]), _i32(a["facets"]), a["n_q"],
-                                                        _f64(a["q_pts"]), _f64(a["q_w"]), a["n_instr"], _i32(a["code"]), a["n_consts"],
-                                                        _f64(a["consts"]), a["n_aux"], _i32(a["aux_mode"]), a["n_out"],
-                                                        C.byref(fid) if a["id"] else None)
-        return rc, int(fid.value)
-
-    def error(self):
-        return (self.be.lib.knp_last_error(self.be.ctx) or b"").decode()
-
-
 def test_every_error_of_the_raw_abi(problems):
     from cgx_hip import _lib
     from cgx_hip._lib import OPS
