@@ -281,7 +281,15 @@ int knp_pc_apply(knp_ctx* ctx, const double* r, double* z); /* r, z: [n_dof_loca
 /* Additive coarse correction for near-null modes the per-GPU preconditioner blocks cannot see (constants of a
  * potential block on a connected component that the partition cuts): z += Z Einv Z^T r with Z the indicator
  * vectors of the potential DoFs of each mode. node_mode: host [n_nodes_owned], -1 = not deflated.
- * Einv: host [n_modes^2] (pseudo-)inverse of Z^T A Z, identical on every rank. n_modes = 0 disables. */
+ * Einv: host [n_modes^2], row-major (pseudo-)inverse of Z^T A Z, identical on every rank: the potential entry of a node of
+ * mode a gains sum_c Einv[a * n_modes + c] * s_c, s_c = the sum of the potential entries of r over the nodes of mode c.
+ * n_modes = 0 disables.  A rejected call (KNP_E_ARG: more than 32 modes, a null array, a mode id outside -1 .. n_modes - 1)
+ * changes nothing: the modes of the last accepted call stay in force.
+ * Dirichlet rows: the correction is added after the copy z = r on the rows of knp_set_dirichlet, so a pinned potential row
+ * that is listed in a mode receives it like any other row of that mode (and its entry of r enters s_c).  B stays non-singular
+ * and the limit of the solve is unchanged, but B is no longer the identity on that row.  Callers that want the identity there
+ * pass -1 for the node (cgx_hip.backend does).  The gauge projection of knp_set_nullspace, when on, follows and shifts every
+ * potential row, pinned or not. */
 int knp_set_deflation(knp_ctx* ctx, int32_t n_modes, const int32_t* node_mode, const double* einv);
 /* AMG hierarchies (hier 0 or 1) supplied level by level (level 0 = finest = P itself, possibly restricted to a
  * field class by zero rows). All arrays HOST; copied. */

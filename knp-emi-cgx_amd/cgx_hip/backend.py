@@ -29,6 +29,22 @@ def _i32(a):
     return a.ctypes.data_as(_lib.i32p)
 
 
+def deflation_node_modes(node_i, node_e, n_vertices_owned, n_nodes_owned, vertex_mode_i, ecs_mode, bc_dofs=None):
+    """``node_mode`` of knp_set_deflation: the mode of every owned node (intracellular: that of its component or -1, extracellular:
+    ``ecs_mode``), and -1 where the node's potential row is a Dirichlet row -- the correction is added after the Dirichlet copy, so a
+    pinned row listed in a mode would not stay an identity row of the preconditioner (include/knpemi_hip.h)."""
+    nvo = n_vertices_owned
+    node_mode = np.full(n_nodes_owned, -1, dtype=np.int32)
+    vi = np.nonzero(node_i[:nvo] >= 0)[0]
+    node_mode[node_i[vi]] = np.asarray(vertex_mode_i)[vi]
+    ve = np.nonzero(node_e[:nvo] >= 0)[0]
+    node_mode[node_e[ve]] = ecs_mode
+    if bc_dofs is not None and len(bc_dofs):
+        bc = np.asarray(bc_dofs, dtype=np.int64)
+        node_mode[bc[(bc & 3) == 3] >> 2] = -1
+    return node_mode
+
+
 class StateUpdate:
     """The state variables of the problem's mechanisms on a backend (``self.p.state_variables``, csrc/knp_states.inc).  Every
     knp_state_* call is counted in ``state_calls``: a problem without states makes none."""
@@ -147,13 +163,14 @@ class Backend(StateUpdate):
         if getattr(problem, "state_variables", None) and all(st.spec is not None for st in problem.state_variables):
             self.state_setup()      # else setup_variational_form() has not compiled them yet: it hands them over
         self.set_sources()
-        self.setup_deflation()
         self.setup_dirichlet()
+        self.setup_deflation()      # after the Dirichlet rows: pinned potential rows stay out of the modes
 
     def setup_dirichlet(self):
         """Dirichlet rows (MMS runs): extracellular unknowns at the exterior-boundary vertices."""
         p = self.p
         self.bc_dofs = None
+        self.bc_dofs_host = None
         if not getattr(p, "bcs", None):
             return
         dofs, vals = [], []
@@ -163,6 +180,7 @@ class Backend(StateUpdate):
             dofs.append(4 * nodes[ok] + f)
             vals.append(np.asarray(values)[ok])
         dofs = np.ascontiguousarray(np.concatenate(dofs), dtype=np.int32)
+        self.bc_dofs_host = dofs
         self.bc_dofs = torch.as_tensor(dofs.astype(np.int64), device=self.device)
         self.bc_vals = torch.as_tensor(np.concatenate(vals), dtype=torch.float64, device=self.device)
         self.check(self.lib.knp_set_dirichlet(self.ctx, len(dofs), _i32(dofs)))
@@ -180,12 +198,8 @@ class Backend(StateUpdate):
         if p.comm.size == 1 or not d or getattr(self, "_skip_deflation", False):
             return
         m = int(d["n_modes"])
-        nvo = lm.n_vertices_owned
-        node_mode = np.full(self.n_nodes_owned, -1, dtype=np.int32)
-        vi = np.nonzero(self.node_i[:nvo] >= 0)[0]
-        node_mode[self.node_i[vi]] = d["vertex_mode_i"][vi]
-        ve = np.nonzero(self.node_e[:nvo] >= 0)[0]
-        node_mode[self.node_e[ve]] = d["ecs_mode"]
+        node_mode = deflation_node_modes(self.node_i, self.node_e, lm.n_vertices_owned, self.n_nodes_owned, d["vertex_mode_i"], d["ecs_mode"],
+                                         self.bc_dofs_host)
         total = d["total_area"]
         if total is None:
             total = p.integrate_over_membrane(1.0, p.gamma_tags)

@@ -4823,13 +4823,14 @@ static int pc_apply_proj(knp_ctx* ctx, const double* r, double* z, int64_t cnt, 
 int knp_set_deflation(knp_ctx* ctx, int32_t n_modes, const int32_t* node_mode, const double* einv) {
     CHECK_CTX(ctx);
     side_discard(ctx);
-    if (n_modes < 0 || n_modes > DEFL_MAX || (n_modes > 0 && (!node_mode || !einv))) { ctx->err = "bad deflation arguments (at most 32 modes)"; return KNP_E_ARG; }
+    if (n_modes < 0 || n_modes > DEFL_MAX) { ctx->err = "bad deflation arguments: n_modes outside 0 .. 32"; return KNP_E_ARG; }
+    if (n_modes > 0 && (!node_mode || !einv)) { ctx->err = "bad deflation arguments: null node_mode or einv"; return KNP_E_ARG; }
+    const int no = ctx->g.n_nodes_owned;
+    for (int n = 0; n_modes > 0 && n < no; ++n)   // every check before the first change: a rejected call leaves the previous modes in force
+        if (node_mode[n] < -1 || node_mode[n] >= n_modes) { ctx->err = "deflation mode id out of range"; return KNP_E_ARG; }
     HIPCHK(hipStreamSynchronize(ctx->stream));
     ctx->defl_m = 0;
     if (n_modes == 0) return KNP_OK;
-    const int no = ctx->g.n_nodes_owned;
-    for (int n = 0; n < no; ++n)
-        if (node_mode[n] < -1 || node_mode[n] >= n_modes) { ctx->err = "deflation mode id out of range"; return KNP_E_ARG; }
     dev_free(ctx->d_defl_mode);
     KCHK(dev_upload_raw(ctx, &ctx->d_defl_mode, node_mode, (size_t)no));
     HIPCHK(hipMemcpy(ctx->d_defl_einv, einv, (size_t)n_modes * n_modes * sizeof(double), hipMemcpyHostToDevice));
