@@ -50,6 +50,9 @@
  *   knp_membrane_functional_create / knp_membrane_functional_eval
  *        dfx.fem.assemble_scalar(dfx.fem.form(<UFL expression> * dS(tag))) with '+' / '-' restrictions, FacetNormal and normal
  *        derivatives: the stimulus current of KNPEMIx_solver.py:580-585, the flux forms of utils/calc_fluxes.py:88
+ *   knp_functional_eval_items / knp_membrane_functional_eval_items / knp_project_apply
+ *        a UFL expression projected or interpolated into a piecewise-constant or P1 space: its value on every cell or facet, and
+ *        the measure-weighted average of those onto the vertices (current density, ion fluxes, channel currents as fields)
  *   knp_emi_*                        the EMI model (src/CGx/EMI): assemble_matrix_block / assemble_vector_block of the forms
  *                                    EMIx_problem.py:152-157, 215-217 and ksp.solve with KSPCG (EMIx_solver.py)
  *   knp_set_comm                     the MPI calls hidden in PETSc/DOLFINx (ghost updates
@@ -584,6 +587,43 @@ int knp_membrane_functional_create(knp_ctx* ctx, int32_t n_tags, const int32_t* 
 int knp_membrane_functional_set_constants(knp_ctx* ctx, int32_t id, int32_t n_consts, const double* consts /* host */);
 int knp_membrane_functional_eval(knp_ctx* ctx, int32_t id, const knp_fields* fields, double* out /* device [n_tags*n_out] */);
 int knp_membrane_functional_destroy(knp_ctx* ctx, int32_t id);
+/* Derived fields: the value of a functional's program on every listed cell or facet, and its average onto the vertices.
+ * knp_functional_eval_items / knp_membrane_functional_eval_items: for a plan of knp_functional_create /
+ *   knp_membrane_functional_create, out[i*n_out + j] = sum_q q_w[q] OUT_j(program at point q of item i), i the item's place in the
+ *   list given at create (cells / facets, whatever order the tags put them in).  That is the item's mean: q_w sums to 1 and the measure
+ *   is not applied.  The kernel is the functional's own with another end: the same loads, geometry, derivative slots and order of
+ *   the sums, one store per item instead of the per-tag reduction, so |T_i| out[i] summed per tag is the functional's value up to the
+ *   order of that sum.  One item per lane, 128 per block, the interpreter's register file in LDS (1 KiB per register the program
+ *   uses, at most 48 KiB).  Enqueued on the library's stream; never waits for the device; the constants of the plan travel as kernel
+ *   arguments.  Only the pointers of slots the code reads are used.  A plan without items is a successful no-op.  KNP_E_ARG with
+ *   nothing launched: an unknown id, null fields or out, a null pointer of a slot the code reads.
+ * Projections: a plan that belongs to the context like a functional (ids of their own; a destroyed id is reused; knp_destroy frees
+ * the plans that are left).
+ * knp_project_create: from the vertices of n_items items (nv each: dim+1 of a cell, dim of a facet) and their measures it builds the
+ *   inverted index on the host -- per vertex the items that hold it, ascending -- and 1 / (sum of the list's measures), 0 for an
+ *   empty list.  Synchronous; 12 bytes per entry and 20 per vertex of device memory.  KNP_E_ARG and no plan: a null argument, nv
+ *   outside 2 .. 4, a vertex outside 0 .. n_vertices-1, a measure that is not finite and positive, an item that lists a vertex twice.
+ * knp_project_apply: out[j*n_vertices + v] = (sum over the items i of v's list, ascending, of measure_i values[i*n_out + j]) /
+ *   (sum of their measures); `fill` where the list is empty.  No atomics: one list per group of L lanes, lane l adds the entries
+ *   l, l + L, .. in order and a fixed shuffle tree adds the lanes; L is the smallest power of two in 2 .. 32 that is not below the mean
+ *   length of the non-empty lists.  A list of more than KNP_PI_SPLIT's value of entries (512) is cut into chunks of that many, each
+ *   summed by a group of its own, and a second kernel adds a list's chunks in order: the same bits on every run.  Enqueued on the
+ *   library's stream; never waits for the device.  KNP_E_ARG with nothing launched: an unknown id, n_out outside 1 .. 3, null values
+ *   or out.
+ * knp_project_get_info: what an application of the plan runs (plan fields only, nothing is launched): the first min(n, KNP_PI_COUNT)
+ *   slots are written.  KNP_E_ARG for a null argument, n <= 0 or an unknown id.
+ * knp_project_destroy: frees the plan (waits for the stream first). */
+int knp_functional_eval_items(knp_ctx* ctx, int32_t id, const knp_fields* fields, double* out /* device [n_items*n_out] */);
+int knp_membrane_functional_eval_items(knp_ctx* ctx, int32_t id, const knp_fields* fields, double* out /* device [n_items*n_out] */);
+enum { KNP_PI_LANES = 0 /* lanes per list, L */, KNP_PI_LONGEST = 1 /* entries of the longest list */,
+       KNP_PI_N_SPLIT = 2 /* lists cut into chunks */, KNP_PI_N_UNITS = 3 /* groups of L lanes launched */,
+       KNP_PI_SPLIT = 4 /* the most entries a list may have without being cut; also the chunk length */, KNP_PI_COUNT = 5 };
+int knp_project_create(knp_ctx* ctx, int32_t n_items, int32_t nv, const int32_t* item_vertices /* host [n_items*nv] */,
+                       const double* measure /* host [n_items] */, int32_t* id /* host */);
+int knp_project_apply(knp_ctx* ctx, int32_t id, const double* values /* device [n_items*n_out] */, int32_t n_out /* 1..3 */, double fill,
+                      double* out /* device [n_out*n_vertices] */);
+int knp_project_get_info(const knp_ctx* ctx, int32_t id, int32_t* out /* host [n] */, int n);
+int knp_project_destroy(knp_ctx* ctx, int32_t id);
 
 /* ---- the EMI model: two potentials with constant conductivities, ONE unknown per node (reference src/CGx/EMI) ----
  * Unknown n is node n of knp_get_layout; every vector is a device array of n_nodes_owned doubles.  One GPU only: every call

@@ -323,6 +323,15 @@ class RunOutput:
             os.makedirs(self.prefix, exist_ok=True)
             buf = torch.zeros((solver.time_steps // interval + 1, len(F.tags), F.n_out), dtype=torch.float64, device=solver.backend.device)
             self.functionals.append({"name": name, "F": F, "interval": interval, "buf": buf})
+        # fields of user expressions (SolverKNPEMI.add_field): fields.xdmf / fields.h5, a pair of its own next to solution.*
+        self.fields, self.fields_writer = list(getattr(solver, "fields", None) or []), None
+        if self.fields:
+            from .fields import FieldsWriter, writer_entry
+            os.makedirs(self.prefix, exist_ok=True)
+            lm = p.local_mesh
+            xname, hname = self._xdmf_names("fields")
+            self.fields_writer = FieldsWriter(xname, hname, lm.coords, np.asarray(lm.cells)[:int(lm.n_cells_owned)],
+                                              [writer_entry(name, F, nodal) for name, F, _, nodal in self.fields])
         self.xdmf = None
         if getattr(solver, "save_xdmfs", False):
             os.makedirs(self.prefix, exist_ok=True)
@@ -375,6 +384,10 @@ class RunOutput:
         for g in self.functionals:
             if i % g["interval"] == 0:
                 g["F"](out=g["buf"][i // g["interval"]])
+        if self.fields_writer is not None:
+            from .fields import record_arrays
+            self.fields_writer.write(float(p.t.value), {name: record_arrays(F, nodal) for name, F, interval, nodal in self.fields
+                                                        if i % interval == 0})
         if s.save_cpoints and (i % s.save_interval == 0):
             self.checkpoint(i)
         if self.xdmf is not None and i > 0 and (i % s.save_interval == 0):       # reference :471
@@ -494,6 +507,11 @@ class RunOutput:
             self._write_solution_xml()
             self.p.print("\nXDMF output saved in ", self.prefix)
             self.xdmf = None
+
+    def close_fields(self):
+        if self.fields_writer is not None:
+            self.fields_writer.close()                 # the .h5 file becomes readable here; fields.xdmf is complete after every record
+            self.fields_writer = None
 
     def checkpoint(self, i):
         """nodal values of the 2(N+1) solution functions (+ phi_m and the gating variables) of this rank's owned vertices"""

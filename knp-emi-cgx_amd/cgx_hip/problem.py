@@ -890,6 +890,18 @@ class ProblemKNPEMI(MixedDimensionalProblem):
         from .functionals import assemble_scalar_membrane
         return assemble_scalar_membrane(self, integrand, tags, degree)
 
+    def cell_field(self, expr_i=None, expr_e=None, tags=None, degree=1, name="field"):
+        """a ``fields.CellField``: the mean of ``expr_i`` / ``expr_e`` on every cell of the chosen tags, kept on the device (the
+        expressions and ``tags`` of ``assemble_scalar``); ``F()`` evaluates it, ``F.to_nodes()`` averages it onto the vertices"""
+        from .fields import CellField
+        return CellField(self, expr_i, expr_e, tags, degree, name)
+
+    def facet_field(self, expr, tags=None, degree=1, name="field"):
+        """a ``fields.FacetField``: the mean of ``expr`` on every membrane facet of the chosen tags, kept on the device (the
+        expressions and ``tags`` of ``assemble_scalar_membrane``)"""
+        from .fields import FacetField
+        return FacetField(self, expr, tags, degree, name)
+
     def print_conservation(self):
         """Total ion amounts and, per intracellular tag, volume, membrane area and charge: the reference's lines
         (KNPEMIx_problem.py:807-843), printed on rank 0 from ``ion_budget()``."""

@@ -129,6 +129,7 @@ class SolverKNPEMI:
                                                                      int(self.save_interval), int(self.time_steps))
         self.out_file_prefix = problem.output_dir
         self.functionals = []      # add_functional(): (name, VolumeFunctional | MembraneFunctional, interval)
+        self.fields = []           # add_field(): (name, CellField | FacetField, interval, nodal)
         self.direct_solver = bool(solver_config["direct"])
         self.view_input = solver_config.get("view_ksp", False)
         norm_set = False
@@ -406,7 +407,8 @@ class SolverKNPEMI:
         from .output import RunOutput
         self.output = RunOutput(self) if (self.save_pngs or self.save_dat or self.save_cpoints or self.save_xdmfs or p.point_evaluation
                                           or self.save_ion_budget or self.save_fluxes
-                                          or self.membrane_potential_tags is not None or self.sample_grids or self.functionals) else None
+                                          or self.membrane_potential_tags is not None or self.sample_grids or self.functionals
+                                          or self.fields) else None
         if self.output is not None:
             self.output.record(0)
 
@@ -593,6 +595,25 @@ class SolverKNPEMI:
             raise ValueError("interval must be at least 1")
         self.functionals.append((name, F, int(interval)))
 
+    def add_field(self, name, F, interval=None, nodal=False):
+        """Record the ``CellField`` or ``FacetField`` ``F`` (cgx_hip/fields.py) at step 0 and at every ``interval``-th step
+        (default ``save_interval``) into fields.xdmf / fields.h5 next to the other outputs: a cell field as a ``Center="Cell"``
+        attribute of the mesh grid, a facet field on a grid ``membrane`` of its facets; ``nodal``: its projection onto the vertices
+        as ``Center="Node"`` attributes instead (``<name>_i`` / ``<name>_e`` of a cell field).  solution.xdmf / solution.h5 are not
+        touched.  Call it before ``solve()`` / ``prepare()``."""
+        from .fields import CellField, FacetField
+        if getattr(self, "_prepared", False):
+            raise RuntimeError("add_field() must be called before solve()")
+        name = str(name)
+        if not name or any(name == n for n, _, _, _ in self.fields):
+            raise ValueError(f"a field needs a name of its own (got '{name}')")
+        if not isinstance(F, (CellField, FacetField)) or F.problem is not self.problem:
+            raise ValueError("add_field() takes a CellField or a FacetField of this solver's problem")
+        interval = self.save_interval if interval is None else interval
+        if int(interval) < 1:
+            raise ValueError("interval must be at least 1")
+        self.fields.append((name, F, int(interval), bool(nodal)))
+
     def solve(self):
         self.prepare()
         try:
@@ -609,6 +630,8 @@ class SolverKNPEMI:
                 pass
             if self.save_xdmfs and getattr(self, "output", None) is not None:
                 self.output.close_xdmf()
+            if self.fields and getattr(self, "output", None) is not None:
+                self.output.close_fields()
 
     def potential_norms(self):
         """L2 norms of phi_i over Omega_i and phi_e over Omega_e (reference main.py:70-84)."""

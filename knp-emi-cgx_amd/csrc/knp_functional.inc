@@ -17,6 +17,8 @@
 //                   measure q_w[q] OUT_j, every output on its own; a slot of mode >= 0 is one number per item, kept in av[k][0].  Then
 //                   the per-tag reduction, the diagnostics' own: diag_chunk_partials, and on the host k_diag_combine and, for the tags of
 //                   more than FN_WAVE_CHUNKS chunks, k_diag_combine_long.  No atomics: the same inputs give the same bits on every run.
+//                   With ITEMS it ends in a plain store instead (knp_fields.inc): the item's mean sum_q q_w[q] OUT_j, measure not
+//                   applied, at dst[i n_out + j] of every live lane.
 //   fn_create, fn_of, fn_set_constants, fn_eval, fn_destroy, fn_free   the plan's life, with the kind's name in the error texts.
 // The volume kind's own:
 //   k_functional    one cell per lane, FN_BT cells per block.  The lane loads its cell's vertices and coordinates and forms |T|.  A slot
@@ -83,8 +85,9 @@ __device__ __forceinline__ void fn_load_fields(const FieldPtrs& f, const FnBind&
 
 // Per quadrature point: interpolate the values and the coordinates x of the item's vertices, run the interpreter and add
 // meas q_w[q] OUT_j, every output on its own; then the diagnostics' per-tag reduction of the block (diag_chunk_partials).  The order of
-// a in the interpolation sums and of q in the accumulation fixes the bits.
-template <int DIM, int NV, int NOUT>
+// a in the interpolation sums and of q in the accumulation fixes the bits.  ITEMS: the weight is q_w[q] alone and the end is one store
+// per live lane, dst = the caller's [n][NOUT]; key is not read.
+template <int DIM, int NV, int NOUT, bool ITEMS>
 __device__ __forceinline__ void fn_integrate(const FnLane& L, int n, const int32_t* __restrict__ key, const FnValues<NV>& U,
                                              const double (*x)[DIM], const FnBind& B, int n_q, const double* __restrict__ qp,
                                              const double* __restrict__ qw, double meas, const int32_t* __restrict__ code, int n_instr,
@@ -129,18 +132,25 @@ __device__ __forceinline__ void fn_integrate(const FnLane& L, int n, const int32
             xq[0][d] = t;
         }
         run_program<1, FN_BT>(code, n_instr, L.sk, kiq, keq, phq, auxq, xq, Iout, L.reg);
-        const double w = qw[q] * meas;
+        const double w = ITEMS ? qw[q] : qw[q] * meas;
 #pragma unroll
         for (int j = 0; j < NOUT; ++j) acc[j] += w * Iout[0][j];
     }
-    DiagSum<NOUT> s;
+    if constexpr (ITEMS) {
+        if (L.live) {
 #pragma unroll
-    for (int j = 0; j < NOUT; ++j) s.v[j] = acc[j];
-    diag_chunk_partials<DiagSum<NOUT>, FN_BT>(L.live ? key[L.i] : -1, L.live, L.i == n - 1, s, partial);
+            for (int j = 0; j < NOUT; ++j) partial[(size_t)L.i * NOUT + j] = acc[j];
+        }
+    } else {
+        DiagSum<NOUT> s;
+#pragma unroll
+        for (int j = 0; j < NOUT; ++j) s.v[j] = acc[j];
+        diag_chunk_partials<DiagSum<NOUT>, FN_BT>(L.live ? key[L.i] : -1, L.live, L.i == n - 1, s, partial);
+    }
 }
 
 // ---- the volume kind's own: the cell load, |T|, grad(lambda) and the derivative slots ---------------------------------------------
-template <int DIM, int NOUT>
+template <int DIM, int NOUT, bool ITEMS = false>
 __global__ void __launch_bounds__(FN_BT) k_functional(int n, const int32_t* __restrict__ item, const int32_t* __restrict__ key,
                                                       const int32_t* __restrict__ cells, const double* __restrict__ coords, int n_q,
                                                       const double* __restrict__ qb, const double* __restrict__ qw, FieldPtrs f, FnBind B,
@@ -188,7 +198,7 @@ __global__ void __launch_bounds__(FN_BT) k_functional(int n, const int32_t* __re
             U.av[k][0] = d;
         }
     }
-    fn_integrate<DIM, DIM + 1, NOUT>(L, n, key, U, x, B, n_q, qb, qw, vol, code, n_instr, partial);
+    fn_integrate<DIM, DIM + 1, NOUT, ITEMS>(L, n, key, U, x, B, n_q, qb, qw, vol, code, n_instr, partial);
 }
 
 // ---- the plan lifecycle both kinds share.  A kind is its name in the error texts and its table of the context: the ids of the two
@@ -291,14 +301,15 @@ static int fn_set_constants(knp_ctx* ctx, const FnKind& kind, int32_t id, int32_
     return KNP_OK;
 }
 
-// Evaluation of either kind: binds the fields the program reads, then launch(D, NOUT, P, f, B, K, lds) is the kind's kernel over the
-// plan's map, and the combines write out.
-template <class Launch>
+// Evaluation of either kind: binds the fields the program reads, then launch(D, NOUT, ITEMS, P, f, B, K, lds, dst) is the kind's kernel
+// over the plan's map, and the combines write out.  ITEMS (knp_fields.inc): the kernel stores every item's mean straight into out
+// (dst = out, [n][n_out] in the plan's item order) and there is no combine; otherwise dst is the map's partials.
+template <bool ITEMS, class Launch>
 static int fn_eval(knp_ctx* ctx, const FnKind& kind, int32_t id, const knp_fields* fields, double* out, Launch launch) {
     KCHK(fn_of(ctx, kind, id));
     const KnpFunctional& P = kind.plans[(size_t)id];
     const KnpDiagMap& m = P.map;
-    if (m.n_tags == 0) return KNP_OK;
+    if (ITEMS ? m.n == 0 : m.n_tags == 0) return KNP_OK;
     if (!fields || !out) { ctx->err = std::string(kind.name) + ": null fields or null output buffer"; return KNP_E_ARG; }
     FieldPtrs f;
     bool missing = false;
@@ -322,13 +333,16 @@ static int fn_eval(knp_ctx* ctx, const FnKind& kind, int32_t id, const knp_field
         DiagConsts K;
         for (int i = 0; i < KNP_DIAG_MAX_CONSTS; ++i) K.v[i] = i < P.n_consts ? P.consts[i] : 0.0;
         const size_t lds = (size_t)std::max(P.n_regs, 1) * FN_BT * sizeof(double);   // <= 48 registers: 48 KiB
+        double* dst = ITEMS ? out : m.d_partial;
+        const std::integral_constant<bool, ITEMS> items;
         by_dim(ctx->g.dim, [&](auto D) {
-            if (P.n_out == 1) launch(D, std::integral_constant<int, 1>(), P, f, B, K, lds);
-            else if (P.n_out == 2) launch(D, std::integral_constant<int, 2>(), P, f, B, K, lds);
-            else launch(D, std::integral_constant<int, 3>(), P, f, B, K, lds);
+            if (P.n_out == 1) launch(D, std::integral_constant<int, 1>(), items, P, f, B, K, lds, dst);
+            else if (P.n_out == 2) launch(D, std::integral_constant<int, 2>(), items, P, f, B, K, lds, dst);
+            else launch(D, std::integral_constant<int, 3>(), items, P, f, B, K, lds, dst);
         });
         HIPCHK(hipGetLastError());
     }
+    if (ITEMS) return KNP_OK;
     if (P.n_out == 1) return diag_combine<DiagSum<1>>(ctx, m, out);
     if (P.n_out == 2) return diag_combine<DiagSum<2>>(ctx, m, out);
     return diag_combine<DiagSum<3>>(ctx, m, out);
@@ -357,6 +371,19 @@ static bool functional_flat_cell(const std::vector<int32_t>& cells, const std::v
         if (!ok) ++bad;
     }
     return bad != 0;
+}
+
+// the volume kind's launch, of either end (fn_eval)
+template <bool ITEMS>
+static int functional_eval(knp_ctx* ctx, int32_t id, const knp_fields* fields, double* out) {
+    return fn_eval<ITEMS>(ctx, fn_volume(ctx), id, fields, out,
+                          [&](auto D, auto NOUT, auto I, const KnpFunctional& P, const FieldPtrs& f, const FnBind& B, const DiagConsts& K, size_t lds,
+                              double* dst) {
+                              const KnpDiagMap& m = P.map;
+                              hipLaunchKernelGGL((k_functional<D(), NOUT(), I()>), dim3(m.n_chunks), dim3(FN_BT), lds, ctx->stream, m.n, m.d_item,
+                                                 m.d_key, ctx->d_cells, ctx->d_coords, P.n_q, P.d_qp, P.d_qw, f, B, P.d_code, P.n_instr, K,
+                                                 P.n_consts, dst);
+                          });
 }
 
 extern "C" {
@@ -391,12 +418,7 @@ int knp_functional_set_constants(knp_ctx* ctx, int32_t id, int32_t n_consts, con
 
 int knp_functional_eval(knp_ctx* ctx, int32_t id, const knp_fields* fields, double* out) {
     CHECK_CTX(ctx);
-    return fn_eval(ctx, fn_volume(ctx), id, fields, out,
-                   [&](auto D, auto NOUT, const KnpFunctional& P, const FieldPtrs& f, const FnBind& B, const DiagConsts& K, size_t lds) {
-                       const KnpDiagMap& m = P.map;
-                       hipLaunchKernelGGL((k_functional<D(), NOUT()>), dim3(m.n_chunks), dim3(FN_BT), lds, ctx->stream, m.n, m.d_item, m.d_key,
-                                          ctx->d_cells, ctx->d_coords, P.n_q, P.d_qp, P.d_qw, f, B, P.d_code, P.n_instr, K, P.n_consts, m.d_partial);
-                   });
+    return functional_eval<false>(ctx, id, fields, out);
 }
 
 int knp_functional_destroy(knp_ctx* ctx, int32_t id) {

@@ -65,6 +65,7 @@ void knp_emi_free(knp_ctx* ctx);
 void knp_state_free(knp_ctx* ctx);
 void knp_sample_free(knp_ctx* ctx);
 void knp_functional_free(knp_ctx* ctx);
+void knp_project_free(knp_ctx* ctx);
 
 // ---- the EMI model (knp_emi.inc): one unknown per node on the graph knp_create built ------------------------------------------
 struct KnpEmi {
@@ -136,6 +137,24 @@ struct KnpFunctional {
     double* d_qp = nullptr;        // [n_q*(dim+1)] barycentric points of the cell rule, or [n_q*dim] of the facet rule
     double* d_qw = nullptr;        // [n_q] weights, sum 1
     double consts[KNP_DIAG_MAX_CONSTS] = {};   // host copy: passed to the kernel by value at every launch
+};
+
+// ---- projection of item values onto vertices (knp_fields.inc): the inverted index of one knp_project_create ---------------------------
+// A unit is what one group of lanes sums: a whole vertex list of at most PROJ_SPLIT entries (an empty one too), or one chunk of a
+// longer list.  Units are in vertex order, a list's chunks in list order, so unit u owns the entries [ubeg[u], ubeg[u + 1]).
+struct KnpProjection {
+    bool live = false;
+    int n_items = 0, n_units = 0, n_split = 0, n_slots = 0;
+    int lanes = 0, longest = 0;    // the lanes per unit chosen at create, the longest list
+    int32_t* d_ubeg = nullptr;     // [n_units+1] first entry of every unit
+    int32_t* d_uvert = nullptr;    // [n_units] the unit's vertex
+    int32_t* d_uslot = nullptr;    // [n_units] -1: the unit writes out; else its slot among the partials
+    int32_t* d_item = nullptr;     // [n_entries] item of every entry: per vertex ascending
+    double* d_meas = nullptr;      // [n_entries] that item's measure
+    double* d_inv = nullptr;       // [n_vertices] 1 / sum of the list's measures, 0 where the list is empty
+    int32_t* d_svert = nullptr;    // [n_split] the vertices of the split lists
+    int32_t* d_sptr = nullptr;     // [n_split+1] their slots: list k owns [sptr[k], sptr[k + 1]), in chunk order
+    double* d_partial = nullptr;   // [n_slots*3] per-chunk sums of the last apply
 };
 
 // ---- device-side program ------------------------------------------------------------------
@@ -475,6 +494,7 @@ struct knp_ctx {
     std::vector<KnpSamplePlan> sample_plans;   // knp_sample_plan_create: the id is the index; a destroyed slot is reused
     std::vector<KnpFunctional> functionals;    // knp_functional_create: likewise
     std::vector<KnpFunctional> membrane_functionals;   // knp_membrane_functional_create: likewise
+    std::vector<KnpProjection> projections;    // knp_project_create: likewise
     // profiling
     int prof_on = 0;
     std::vector<hipEvent_t> prof_pool;   // recycled timing events

@@ -3102,6 +3102,7 @@ int knp_destroy(knp_ctx* ctx) {
     knp_state_free(ctx);
     knp_sample_free(ctx);
     knp_functional_free(ctx);
+    knp_project_free(ctx);
     delete ctx;
     return KNP_OK;
 }
@@ -5161,3 +5162,5 @@ int knp_amg_get_level_info(const knp_ctx* ctx, int32_t hier, int32_t level, int3
 #include "knp_functional.inc"
 // membrane functionals: per-tag integrals over membrane facets of a bytecode program with one-sided gradients and the normal
 #include "knp_membrane_functional.inc"
+// derived fields: the value of a functional's program per cell / facet, and its measure-weighted average onto the vertices
+#include "knp_fields.inc"
