@@ -141,7 +141,11 @@ typedef struct {
     int32_t n_vertices;       /* local vertices, owned first */
     int32_t n_vertices_owned; /* == n_vertices on one GPU */
     int32_t n_cells;
-    int32_t n_cells_owned;    /* owned cells come first; used by knp_l2_norms only */
+    int32_t n_cells_owned;    /* owned cells come first.  The library bounds by it knp_l2_norms, the cell tag map of
+                                 knp_diag_set_cell_tags, the cell maps of the volume functionals and the cells the sampler's point
+                                 locator searches; the host side selects derived fields and output by the same count.  A value
+                                 <= 0 or > n_cells reads as n_cells in all of these (callers that describe a whole mesh may leave it
+                                 0): a rank that owns vertices but no cell cannot say so and must not use those entry points */
     const int32_t* cells;     /* host [n_cells*(dim+1)] local vertex ids */
     const double* coords;     /* host [n_vertices*dim], metres */
     const uint8_t* cell_side; /* host [n_cells] 0 = intracellular, 1 = extracellular */
@@ -266,6 +270,8 @@ int knp_assemble_matrix(knp_ctx* ctx, const knp_fields* fields);
  * while it runs.  The fields must not be modified until the next call that needs A (knp_gmres_solve, knp_spmv, exports), which
  * joins it.  In line (== knp_assemble_matrix) on the first assembly, with vertex-block Jacobi or when kernel classes are timed. */
 int knp_assemble_matrix_async(knp_ctx* ctx, const knp_fields* fields);
+/* writes the owned entries [0, n_dof_owned) of b -- membrane facets this rank sees but does not own contribute to its owned rows --
+ * and leaves the ghost entries [n_dof_owned, n_dof_local) as they are */
 int knp_assemble_rhs(knp_ctx* ctx, const knp_fields* fields, double* b /* device [n_dof_local] */);
 int knp_assemble_precond(knp_ctx* ctx, const knp_fields* fields);
 /* form of the potential block of P: 0 the reference's (- (C_M/F) M_Gamma per side, sides uncoupled, KNPEMIx_problem.py:735-738),
