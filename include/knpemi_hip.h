@@ -400,7 +400,23 @@ int knp_unpack(knp_ctx* ctx, const double* x, const knp_fields_out* fields);
  * knp_fields_unchanged: the caller's promise that nobody has written the concentration fields of the target since the last
  * knp_unpack.  One shot: the next knp_assemble_matrix(_async) -- given the same six concentration pointers -- then skips its
  * node-indexed copy pass if the solve's tail has already written it, and the promise is consumed either way.
- * KNP_ST_FUSED_TAILS / KNP_ST_KNOD_SKIPS count both. */
+ * KNP_ST_FUSED_TAILS / KNP_ST_KNOD_SKIPS count both.
+ * Assembly ahead (KNP_ASM_AHEAD, read at knp_pc_setup: 0 never, 1 (default) where the SpMV's streams and the second buffer below fit
+ * the 256 MiB Infinity Cache together, 84 B per node pair + 128 B per membrane vertex pair, 2 whatever the size).  A matrix assembly that skipped the copy pass ARMS the context: the
+ * caller has just shown the pattern "unpack, fields untouched, assemble".  While armed, a knp_gmres_solve that ends in the fused tail
+ * enqueues the next step's matrix assembly itself, on the library's assembly stream behind its last kernel, reading the concentration
+ * fields and phi_m of the registered target -- when only the solution-dependent entries are due (same dt as the last assembly, not
+ * KNP_ASM_FULL), with an AMG preconditioner, no Dirichlet rows, one GPU without hooks or peer-to-peer plans and no kernel-class timing
+ * beyond the SpMV's.  It writes a second buffer (same size as the solution-dependent entries, allocated at the first such assembly; if
+ * that fails the context goes on without the feature), so the matrix of the step just solved stays what knp_spmv, knp_get_csr_values
+ * and every other reader see.  The next knp_assemble_matrix(_async) ADOPTS the result -- swaps the buffers and launches nothing;
+ * counted in KNP_ST_KNOD_SKIPS there -- iff the promise above was given, the six concentration pointers and phi_m are the target's
+ * and dt and the conditions still hold.  Otherwise the result is DISCARDED, the context disarmed, and the assembly runs as without
+ * the feature: a caller that writes the fields every step pays one wasted assembly each time the pattern breaks, plus one after the
+ * last step of a run.  Every entry listed above as forgetting the target, and knp_set_params, discards a pending result as well.
+ * Between the solve and the promise the library's kernels may READ the fields while the caller writes them: harmless, since no index
+ * depends on a value and a caller that wrote withholds the promise, so what was read is never used.
+ * KNP_ST_AHEAD_ADOPTED / KNP_ST_AHEAD_DISCARDED count both outcomes. */
 int knp_set_unpack_target(knp_ctx* ctx, const knp_fields_out* fields /* or NULL */);
 int knp_fields_unchanged(knp_ctx* ctx);
 /* test hook: the node-indexed concentration copy {k0, k1, k2, 0} per local node, host [4 * n_nodes] (synchronises; KNP_E_STATE on
@@ -701,7 +717,9 @@ enum { KNP_ST_BNORM = 0 /* ||B b|| of the last solve */, KNP_ST_ALLREDUCE = 1 /*
        KNP_ST_SPMV_DOTS = 9 /* reductions whose first stage ran in the SpMV on A (knp_fgmres_solve, KNP_SPMV_DOTS) */,
        KNP_ST_FUSED_TAILS = 10 /* solves whose last update also unpacked x (knp_set_unpack_target, KNP_FUSED_TAIL) */,
        KNP_ST_KNOD_SKIPS = 11 /* matrix assemblies that skipped the node-indexed concentration copy (knp_fields_unchanged) */,
-       KNP_ST_COUNT = 12 };
+       KNP_ST_AHEAD_ADOPTED = 12 /* matrix assemblies taken from the one enqueued at the end of the last solve (KNP_ASM_AHEAD) */,
+       KNP_ST_AHEAD_DISCARDED = 13 /* such assemblies that ran for nothing */,
+       KNP_ST_COUNT = 14 };
 int knp_get_stats(const knp_ctx* ctx, double* out /* host [KNP_ST_COUNT] */);
 /* bytes the kernels of one application must move, from the sizes of the arrays they read and write (per-class roofline): [0] SpMV on A,
  * [1] one preconditioner application, [2] matrix assembly of one step, [3] right-hand side assembly, [4] one owned vector */

@@ -791,11 +791,12 @@ class Backend(StateUpdate):
 
     def stats(self):
         """||B b|| of the last solve and the exchange / read-back counters since the last ``profile_reset``."""
-        out = (C.c_double * 12)()   # KNP_ST_COUNT
+        out = (C.c_double * 14)()   # KNP_ST_COUNT
         self.check(self.lib.knp_get_stats(self.ctx, out))
         return {"bnorm": out[0], "allreduces": int(out[1]), "halos": int(out[2]), "readbacks": int(out[3]), "fused": int(out[4]),
                 "norm_fallbacks": int(out[5]), "blocked": int(out[6]), "fused_levels": int(out[7]),
-                "fused_dots": int(out[8]), "spmv_dots": int(out[9]), "fused_tails": int(out[10]), "knod_skips": int(out[11])}
+                "fused_dots": int(out[8]), "spmv_dots": int(out[9]), "fused_tails": int(out[10]), "knod_skips": int(out[11]),
+                "asm_ahead": int(out[12]), "asm_ahead_discarded": int(out[13])}
 
     def nodal_conc(self):
         """the library's node-indexed copy of the concentrations, [n_nodes, 4] on the host (test hook, synchronises)"""

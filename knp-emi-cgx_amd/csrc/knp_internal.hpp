@@ -475,6 +475,25 @@ struct knp_ctx {
     bool knod_skipped = false;       // the last matrix assembly skipped k_nodal_conc (knp_get_traffic_model)
     int64_t n_fused_tail = 0;        // solves that ended in k_lincomb_unpack
     int64_t n_knod_skip = 0;         // matrix assemblies that skipped k_nodal_conc
+    // Matrix assembly ahead of the caller (KNP_ASM_AHEAD; speculate_asm, adopt_ahead): a solve that ended in k_lincomb_unpack enqueues
+    // the next step's time-dependent assembly on stream_asm, into the ALTERNATE buffers d_at_alt / d_ax_alt, so that A of the step just
+    // solved stays readable.  The next knp_assemble_matrix(_async) adopts it (swaps the buffers, launches nothing) iff the caller gave
+    // the promise and passes the recorded pointers with the recorded dt; otherwise it is discarded.  `asm_armed`: the last matrix
+    // assembly, normal or adopted, took the skip path, i.e. the caller leaves the fields alone between unpack and assembly; cleared by
+    // every discard, so a caller that writes the fields pays one wasted assembly each time the pattern breaks.  A pending speculation is
+    // DROPPED (drop_ahead: joined, counted as discarded) by every entry that clears knod_current above and by knp_set_params.
+    int asm_ahead = 1;               // KNP_ASM_AHEAD (read at knp_pc_setup): 0 off, 1 where both copies fit the Infinity Cache next to the SpMV's streams, 2 always
+    bool asm_armed = false;
+    bool asm_alt_failed = false;     // the alternate buffers could not be allocated: this context never assembles ahead
+    double *d_at_alt = nullptr, *d_ax_alt = nullptr;   // allocated (NaN-filled) at the first speculation
+    struct AsmAhead {
+        bool pending = false;
+        const double* k_i[3] = {nullptr, nullptr, nullptr};
+        const double* k_e[3] = {nullptr, nullptr, nullptr};
+        const double* phi_m = nullptr;
+        double dt = 0.0;
+    } ahead;
+    int64_t n_ahead_adopted = 0, n_ahead_discarded = 0;
     // step timers (knp_timer_mark / knp_timer_read): timing events recorded on the main stream, read back in one go
     std::vector<hipEvent_t> tm_events;
     size_t tm_used = 0;

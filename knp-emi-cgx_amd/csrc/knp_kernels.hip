@@ -71,6 +71,8 @@ static void side_discard(knp_ctx* ctx);
 static DevParams make_params(const knp_ctx* ctx);
 static int64_t phi_block_nnz(const knp_ctx* ctx);
 static int join_asm(knp_ctx* ctx);
+static int drop_ahead(knp_ctx* ctx);
+static int speculate_asm(knp_ctx* ctx);
 static bool fin_ok(const knp_ctx* ctx);
 static hipEvent_t prof_event(knp_ctx* ctx);
 static void free_hier(KnpAmgHier& H);
@@ -460,7 +462,7 @@ static void launch_cell_means(knp_ctx* ctx, const FieldPtrs& f, bool matrix = fa
     ctx->fields_promise = false;
     ctx->knod_current = false;
     if (matrix) ctx->knod_skipped = skip;
-    if (skip) { ++ctx->n_knod_skip; return; }
+    if (skip) { ++ctx->n_knod_skip; ctx->asm_armed = true; return; }   // (armed: the next solve's tail may assemble ahead)
     if (ctx->asm_dmax > 0)
         hipLaunchKernelGGL(k_nodal_conc, dim3(nblocks(g.n_nodes)), dim3(NT), 0, ctx->stream, g.n_nodes, ctx->d_node_vertex, ctx->d_node_side, f, ctx->d_knod);
     else
@@ -3063,6 +3065,7 @@ int knp_create(knp_ctx** out, const knp_mesh_desc* mesh) {
 int knp_destroy(knp_ctx* ctx) {
     if (!ctx) return KNP_OK;
     (void)hipDeviceSynchronize();
+    if (ctx->stream_asm) (void)hipStreamSynchronize(ctx->stream_asm);   // a speculative assembly nobody asked for any more
     if (ctx->stream2) { (void)hipEventDestroy(ctx->ev_fork); (void)hipEventDestroy(ctx->ev_join); (void)hipStreamDestroy(ctx->stream2); }
     if (ctx->stream3) { (void)hipEventDestroy(ctx->ev_x); (void)hipEventDestroy(ctx->ev_halo); (void)hipStreamDestroy(ctx->stream3); }
     if (ctx->stream_asm) { (void)hipEventDestroy(ctx->ev_fork_asm); (void)hipEventDestroy(ctx->ev_asm); (void)hipStreamDestroy(ctx->stream_asm); }
@@ -3084,7 +3087,7 @@ int knp_destroy(knp_ctx* ctx) {
     dev_free(ctx->d_gv_vertex); dev_free(ctx->d_gv_node_i); dev_free(ctx->d_gv_node_e); dev_free(ctx->d_node_gv);
     dev_free(ctx->d_gptr); dev_free(ctx->d_gcol); dev_free(ctx->d_grow); dev_free(ctx->d_gq_i); dev_free(ctx->d_gq_e);
     dev_free(ctx->d_gdiag); dev_free(ctx->d_gcptr); dev_free(ctx->d_gc_facet); dev_free(ctx->d_gc_lab);
-    dev_free(ctx->d_at); dev_free(ctx->d_ac); dev_free(ctx->d_ax); dev_free(ctx->d_gx_i); dev_free(ctx->d_gx_e);
+    dev_free(ctx->d_at); dev_free(ctx->d_ac); dev_free(ctx->d_ax); dev_free(ctx->d_at_alt); dev_free(ctx->d_ax_alt); dev_free(ctx->d_gx_i); dev_free(ctx->d_gx_e);
     dev_free(ctx->d_p_vals); dev_free(ctx->d_px);
     dev_free(ctx->d_cbar); dev_free(ctx->d_fmat); dev_free(ctx->d_fvec);
     dev_free(ctx->d_partial); dev_free(ctx->d_red); dev_free(ctx->d_y); dev_free(ctx->d_vbj); dev_free(ctx->d_gm);
@@ -3230,6 +3233,7 @@ int knp_set_params(knp_ctx* ctx, double dt, double F, double C_M, double psi, in
     CHECK_CTX(ctx);
     if (n_ions != 3 || !z || !Di || !De) { ctx->err = "n_ions must be 3 (Na, K, Cl; KNPEMIx_problem.py:980-981)"; return KNP_E_ARG; }
     if (!(dt > 0) || !(psi > 0) || F == 0.0) { ctx->err = "dt, psi must be positive and F non-zero"; return KNP_E_ARG; }
+    KCHK(drop_ahead(ctx));   // assembled with the parameters as they were
     ctx->dt = dt; ctx->F = F; ctx->C_M = C_M; ctx->psi = psi; ctx->n_ions = 3;
     ctx->asm_dt = -1.0;   // constant blocks must be rewritten
     for (int j = 0; j < 3; ++j) {
@@ -3340,6 +3344,7 @@ int knp_set_dirichlet(knp_ctx* ctx, int32_t n, const int32_t* dofs) {
     }
     ctx->asm_dt = -1.0;   // constant blocks of the touched rows must be rewritten if the set changes
     ctx->fields_current = ctx->knod_current = false;
+    KCHK(drop_ahead(ctx));
     return KNP_OK;
 }
 
@@ -3384,18 +3389,20 @@ static int join_asm(knp_ctx* ctx) {
     return KNP_OK;
 }
 
-static int assemble_matrix_on_stream(knp_ctx* ctx, const knp_fields* fields, bool with_schur_diag) {
+// `at`, `ax`: where the solution-dependent entries go (ctx->d_at / d_ax, or the alternate pair of a speculative assembly, which is
+// the time-dependent form only and finds d_knod current: `knod_ready`)
+static int assemble_matrix_on_stream(knp_ctx* ctx, const knp_fields* fields, bool with_schur_diag, double* at, double* ax, bool knod_ready = false) {
     const KnpHostGraph& g = ctx->g;
     const DevParams P = make_params(ctx);
     FieldPtrs f = make_fields(fields);
     ProfScope ps(ctx, 3);
-    launch_cell_means(ctx, f, true);
+    if (!knod_ready) launch_cell_means(ctx, f, true);
     // The (k,k) and (phi,k) blocks do not depend on the previous solution (SURVEY 3.2 obs. 1): after the first
     // assembly only the K[k_prev]-type and membrane entries are rewritten, unless KNP_ASM_FULL=1 asks for the
     // reference's behaviour (A.zeroEntries() + full re-assembly, KNPEMIx_solver.py:110-115).
     const bool td_only = ctx->have_A && !ctx->asm_full && ctx->asm_dt == ctx->dt;
-    if (td_only) launch_assemble_nodes<false, true>(ctx, P, ctx->d_at, ctx->d_ac);
-    else launch_assemble_nodes<false, false>(ctx, P, ctx->d_at, ctx->d_ac);
+    if (td_only) launch_assemble_nodes<false, true>(ctx, P, at, ctx->d_ac);
+    else launch_assemble_nodes<false, false>(ctx, P, at, ctx->d_ac);
     ctx->asm_dt = ctx->dt;
     if (g.n_g > 0) {
         if (g.dim == 2)
@@ -3419,11 +3426,11 @@ static int assemble_matrix_on_stream(knp_ctx* ctx, const knp_fields* fields, boo
             hipLaunchKernelGGL((k_gamma_pairs<false>), dim3(nblocks(ctx->n_gp)), dim3(NT), 0, ctx->stream, ctx->n_gp, g.n_g, g.dim, P,
                                ctx->d_grow, ctx->d_gptr, ctx->d_gv_node_i, ctx->d_gv_node_e, ctx->d_gq_i, ctx->d_gq_e,
                                ctx->d_gcptr, ctx->d_gc_facet, ctx->d_gc_lab, ctx->d_fmeas, ctx->d_fmat, ctx->d_pair_ptr,
-                               ctx->d_at, ctx->d_ax);
+                               at, ax);
     }
     if (ctx->n_bc > 0)
         hipLaunchKernelGGL(k_dirichlet_rows_A, dim3(nblocks(ctx->n_bc)), dim3(NT), 0, ctx->stream, ctx->n_bc, ctx->d_bc_dofs, ctx->d_pair_ptr,
-                           ctx->d_pair_col, ctx->d_node_gv, ctx->d_node_side, ctx->d_gptr, ctx->d_ac, ctx->d_at, ctx->d_ax);
+                           ctx->d_pair_col, ctx->d_node_gv, ctx->d_node_side, ctx->d_gptr, ctx->d_ac, at, ax);
     // The Schur diagonal depends on the fields only.  knp_assemble_rhs of the same step has already written it; while a
     // side-stream preconditioner application (knp_gmres_prepare) is in flight it READS d_cc, so it must not be rewritten here
     // (nor by the asynchronous form, which runs next to the right-hand side assembly that writes it).
@@ -3432,18 +3439,119 @@ static int assemble_matrix_on_stream(knp_ctx* ctx, const knp_fields* fields, boo
     ctx->have_A = true;
     if (ctx->pc_kind == KNP_PC_VBJACOBI) {
         hipLaunchKernelGGL(k_vbj_extract, dim3(nblocks(g.n_nodes_owned)), dim3(NT), 0, ctx->stream, g.n_nodes_owned,
-                           ctx->d_pair_ptr, ctx->d_pair_col, ctx->d_ac, ctx->d_at, ctx->d_ax, ctx->d_node_gv, ctx->d_node_side,
+                           ctx->d_pair_ptr, ctx->d_pair_col, ctx->d_ac, at, ax, ctx->d_node_gv, ctx->d_node_side,
                            ctx->d_gdiag, ctx->d_vbj);
         HIPCHK(hipGetLastError());
     }
     return KNP_OK;
 }
 
+// ---- matrix assembly ahead of the caller (KNP_ASM_AHEAD) ----
+// The form that may run ahead, and be adopted: the time-dependent entries only, no Dirichlet rows, one GPU without hooks or
+// peer-to-peer plans, an AMG preconditioner (vertex-block Jacobi consumes A at assembly time), no kernel-class timing beyond the SpMV's.
+static bool ahead_form_ok(const knp_ctx* ctx) {
+    return ctx->asm_ahead && ctx->have_A && !ctx->asm_full && ctx->asm_dt == ctx->dt && ctx->n_bc == 0 && !ctx->halo && !ctx->allreduce &&
+           !ctx->level_comm && !ctx->p2p && (ctx->pc_kind == KNP_PC_AMG || ctx->pc_kind == KNP_PC_AMG_BT || ctx->pc_kind == KNP_PC_AMG_LT) &&
+           (ctx->prof_on & ~1) == 0;
+}
+static bool asm_async_off() {   // KNP_ASM_ASYNC=0: no assembly on a stream of its own, asked for or ahead
+    static const bool off = getenv("KNP_ASM_ASYNC") && atoi(getenv("KNP_ASM_ASYNC")) == 0;
+    return off;
+}
+static int ensure_asm_stream(knp_ctx* ctx) {
+    if (!ctx->stream_asm) {
+        HIPCHK(hipStreamCreateWithFlags(&ctx->stream_asm, hipStreamNonBlocking));
+        HIPCHK(hipEventCreateWithFlags(&ctx->ev_fork_asm, hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&ctx->ev_asm, hipEventDisableTiming));
+    }
+    return KNP_OK;
+}
+// a pending speculative assembly whose inputs are about to change, or that nobody can use: joined (its kernels read the fields and
+// d_knod and use the facet matrices as scratch), counted, and the context disarmed
+static int drop_ahead(knp_ctx* ctx) {
+    if (!ctx->ahead.pending) return KNP_OK;
+    ctx->ahead.pending = false;
+    ctx->asm_armed = false;
+    ++ctx->n_ahead_discarded;
+    return join_asm(ctx);
+}
+// Called by knp_gmres_solve right behind k_lincomb_unpack, which has left the fields of the registered target and d_knod as the next
+// matrix assembly reads them: that assembly goes to the assembly stream now, into the alternate buffers (A of this step stays where
+// every reader finds it).  Nothing here waits; the first call allocates the alternate buffers.
+static int speculate_asm(knp_ctx* ctx) {
+    if (!ctx->asm_armed || !ahead_form_ok(ctx) || !ctx->knod_current || !ctx->have_tail_target || ctx->asm_pending || ctx->ahead.pending ||
+        ctx->prep.left() || ctx->asm_alt_failed || asm_async_off())
+        return KNP_OK;
+    // Two copies of the solution-dependent entries alternate from step to step.  Where the SpMV's streams (52 B per node pair) and
+    // the second copy (32 B per pair, 64 B per membrane vertex pair) do not fit the 256 MiB Infinity Cache together, the assembly
+    // into the other copy can evict what the next solve reads, and the host hole it fills is a fixed ~10 us: 512^2 (155 MB) gains,
+    // cube 64^3 (344 MB) showed no gain -- 7 of 8 alternated pairs 2-20 us slower in three jobs, level in a fourth (DESIGN section
+    // 3) -- so such contexts keep assembling when asked, and allocate no second buffer.  KNP_ASM_AHEAD=2 lifts the bound.
+    if (ctx->asm_ahead < 2 && 84.0 * (double)ctx->n_pairs + 128.0 * (double)ctx->n_gp > 256.0 * 1048576.0) return KNP_OK;
+    KCHK(ensure_asm_stream(ctx));
+    if (!ctx->d_at_alt) {
+        const size_t nat = (size_t)std::max<int64_t>(4 * ctx->n_pairs, 2) * sizeof(double), nax = (size_t)std::max<int64_t>(8 * ctx->n_gp, 2) * sizeof(double);
+        if (hipMalloc((void**)&ctx->d_at_alt, nat) != hipSuccess || hipMalloc((void**)&ctx->d_ax_alt, nax) != hipSuccess) {
+            (void)hipGetLastError();   // no room for a second buffer: this context assembles when asked, as before
+            dev_free(ctx->d_at_alt); dev_free(ctx->d_ax_alt);
+            ctx->asm_alt_failed = true;
+            return KNP_OK;
+        }
+        // NaN (all bits set) wherever the assembly does not write
+        HIPCHK(hipMemsetAsync(ctx->d_at_alt, 0xff, nat, ctx->stream_asm));
+        HIPCHK(hipMemsetAsync(ctx->d_ax_alt, 0xff, nax, ctx->stream_asm));
+    }
+    knp_fields f = {};
+    for (int j = 0; j < 3; ++j) { f.k_i[j] = ctx->tail_target.k_i[j]; f.k_e[j] = ctx->tail_target.k_e[j]; }
+    f.phi_m = ctx->tail_target.phi_m;
+    HIPCHK(hipEventRecord(ctx->ev_fork_asm, ctx->stream));
+    HIPCHK(hipStreamWaitEvent(ctx->stream_asm, ctx->ev_fork_asm, 0));
+    hipStream_t main_stream = ctx->stream;
+    ctx->stream = ctx->stream_asm;
+    const int rc = assemble_matrix_on_stream(ctx, &f, false, ctx->d_at_alt, ctx->d_ax_alt, true);
+    ctx->stream = main_stream;
+    KCHK(rc);
+    HIPCHK(hipEventRecord(ctx->ev_asm, ctx->stream_asm));
+    ctx->asm_pending = true;
+    ctx->ahead.pending = true;
+    for (int j = 0; j < 3; ++j) { ctx->ahead.k_i[j] = f.k_i[j]; ctx->ahead.k_e[j] = f.k_e[j]; }
+    ctx->ahead.phi_m = f.phi_m;
+    ctx->ahead.dt = ctx->dt;
+    return KNP_OK;
+}
+// At the top of a matrix assembly: take the speculative result if it is the assembly asked for -- the caller's promise, the recorded
+// pointers and dt, the form still eligible -- by swapping the buffers; nothing is launched and asm_pending stays as it is (the next
+// reader of A joins).  Otherwise the speculation is dropped and the caller's assembly runs as ever.
+static int adopt_ahead(knp_ctx* ctx, const knp_fields* fields, bool* adopted) {
+    *adopted = false;
+    if (!ctx->ahead.pending) return KNP_OK;
+    bool ok = ctx->fields_promise && ctx->knod_current && ahead_form_ok(ctx) && ctx->ahead.dt == ctx->dt && fields->phi_m == ctx->ahead.phi_m;
+    for (int j = 0; j < 3 && ok; ++j) ok = fields->k_i[j] == ctx->ahead.k_i[j] && fields->k_e[j] == ctx->ahead.k_e[j];
+    if (!ok) return drop_ahead(ctx);
+    std::swap(ctx->d_at, ctx->d_at_alt);
+    std::swap(ctx->d_ax, ctx->d_ax_alt);
+    ctx->ahead.pending = false;
+    ctx->fields_promise = false;
+    ctx->knod_current = false;
+    ctx->knod_skipped = true;   // counted here, where the caller's assembly is: the copy pass it would have run is the one skipped
+    ++ctx->n_knod_skip;
+    ++ctx->n_ahead_adopted;
+    *adopted = true;
+    return KNP_OK;
+}
+
 int knp_assemble_matrix(knp_ctx* ctx, const knp_fields* fields) {
     CHECK_CTX(ctx);
     KCHK(check_fields(ctx, fields, false));
+    bool adopted = false;
+    KCHK(adopt_ahead(ctx, fields, &adopted));
     KCHK(join_asm(ctx));
-    return assemble_matrix_on_stream(ctx, fields, true);
+    if (adopted) {   // the in-line form also refreshes the Schur diagonal (see assemble_matrix_on_stream)
+        if (!ctx->prep.left()) launch_schur_diag(ctx, make_fields(fields));
+        HIPCHK(hipGetLastError());
+        return KNP_OK;
+    }
+    return assemble_matrix_on_stream(ctx, fields, true, ctx->d_at, ctx->d_ax);
 }
 
 // The same assembly on the library's own stream: it depends on the previous solution only, not on the gating update or the
@@ -3453,20 +3561,18 @@ int knp_assemble_matrix(knp_ctx* ctx, const knp_fields* fields) {
 int knp_assemble_matrix_async(knp_ctx* ctx, const knp_fields* fields) {
     CHECK_CTX(ctx);
     KCHK(check_fields(ctx, fields, false));
+    bool adopted = false;
+    KCHK(adopt_ahead(ctx, fields, &adopted));
+    if (adopted) return KNP_OK;   // already on the assembly stream, since the end of the last solve
     KCHK(join_asm(ctx));
-    static const bool off = getenv("KNP_ASM_ASYNC") && atoi(getenv("KNP_ASM_ASYNC")) == 0;
-    if (off || ctx->pc_kind == KNP_PC_VBJACOBI || (ctx->prof_on & ~1) || !ctx->have_A || ctx->prep.left())
-        return assemble_matrix_on_stream(ctx, fields, true);
-    if (!ctx->stream_asm) {
-        HIPCHK(hipStreamCreateWithFlags(&ctx->stream_asm, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&ctx->ev_fork_asm, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&ctx->ev_asm, hipEventDisableTiming));
-    }
+    if (asm_async_off() || ctx->pc_kind == KNP_PC_VBJACOBI || (ctx->prof_on & ~1) || !ctx->have_A || ctx->prep.left())
+        return assemble_matrix_on_stream(ctx, fields, true, ctx->d_at, ctx->d_ax);
+    KCHK(ensure_asm_stream(ctx));
     HIPCHK(hipEventRecord(ctx->ev_fork_asm, ctx->stream));            // after everything that wrote the fields (unpack)
     HIPCHK(hipStreamWaitEvent(ctx->stream_asm, ctx->ev_fork_asm, 0));
     hipStream_t main_stream = ctx->stream;
     ctx->stream = ctx->stream_asm;
-    const int rc = assemble_matrix_on_stream(ctx, fields, false);
+    const int rc = assemble_matrix_on_stream(ctx, fields, false, ctx->d_at, ctx->d_ax);
     ctx->stream = main_stream;
     KCHK(rc);
     HIPCHK(hipEventRecord(ctx->ev_asm, ctx->stream_asm));
@@ -3531,6 +3637,7 @@ int knp_get_precond_phi_csr(const knp_ctx* cctx, int32_t* rp, int32_t* ci, doubl
 int knp_assemble_precond(knp_ctx* ctx, const knp_fields* fields) {
     CHECK_CTX(ctx);
     side_discard(ctx);
+    KCHK(drop_ahead(ctx));   // d_knod is rewritten below
     KCHK(join_asm(ctx));
     KCHK(check_fields(ctx, fields, false));
     const KnpHostGraph& g = ctx->g;
@@ -3732,6 +3839,7 @@ int knp_project_nullspace(knp_ctx* ctx, double* v) {
     side_discard(ctx);
     if (!v) return KNP_E_ARG;
     ctx->fields_current = ctx->knod_current = false;   // v may be the x the last solve unpacked
+    KCHK(drop_ahead(ctx));
     return project_ns(ctx, v);
 }
 
@@ -4645,7 +4753,9 @@ int knp_pc_setup(knp_ctx* ctx, int32_t kind) {
     ctx->gmres_ahead = !(getenv("KNP_GMRES_AHEAD") && atoi(getenv("KNP_GMRES_AHEAD")) == 0);
     ctx->fused_tail = !(getenv("KNP_FUSED_TAIL") && atoi(getenv("KNP_FUSED_TAIL")) == 0);
     ctx->update_early = !(getenv("KNP_UPDATE_EARLY") && atoi(getenv("KNP_UPDATE_EARLY")) == 0);
+    ctx->asm_ahead = getenv("KNP_ASM_AHEAD") ? std::max(atoi(getenv("KNP_ASM_AHEAD")), 0) : 1;   // 0 off, 1 where it fits the cache, 2 always
     ctx->fields_current = ctx->knod_current = false;
+    KCHK(drop_ahead(ctx));
     for (int h = 0; h < KNP_MAX_HIER; ++h) ctx->hier[h].fused = 0;
     if (kind == KNP_PC_AMG) ctx->hier[0].fused = fused_eligible(ctx, ctx->hier[0]) ? 1 : 0;
     if (kind == KNP_PC_AMG_BT || kind == KNP_PC_AMG_LT) {   // both or none: the potential hierarchy then works on compact vectors
@@ -4872,6 +4982,7 @@ static bool same_target(const knp_ctx* ctx, const knp_fields_out* f) {
 int knp_set_unpack_target(knp_ctx* ctx, const knp_fields_out* f) {
     CHECK_CTX(ctx);
     ctx->fields_current = ctx->knod_current = ctx->fields_promise = false;
+    KCHK(drop_ahead(ctx));
     ctx->have_tail_target = false;
     if (!f) return KNP_OK;
     OutPtrs o;
@@ -4900,6 +5011,7 @@ int knp_pack(knp_ctx* ctx, const knp_fields_out* f, double* x) {
     OutPtrs o;
     KCHK(out_ptrs(ctx, f, o, false));
     ctx->fields_current = ctx->knod_current = false;
+    KCHK(drop_ahead(ctx));
     hipLaunchKernelGGL(k_pack, dim3(nblocks(ctx->g.n_nodes)), dim3(NT), 0, ctx->stream, ctx->g.n_nodes, ctx->d_node_vertex,
                        ctx->d_node_side, o, x);
     HIPCHK(hipGetLastError());
@@ -4912,6 +5024,7 @@ int knp_unpack(knp_ctx* ctx, const double* x, const knp_fields_out* f) {
     KCHK(out_ptrs(ctx, f, o, true));
     if (ctx->fields_current && x == ctx->tail_x && same_target(ctx, f)) return KNP_OK;   // the solve's tail has written exactly this
     ctx->fields_current = ctx->knod_current = false;
+    KCHK(drop_ahead(ctx));
     KCHK(join_asm(ctx));   // the fields written here are what an assembly still in flight reads
     KCHK(halo_update(ctx, const_cast<double*>(x)));
     hipLaunchKernelGGL(k_unpack, dim3(nblocks(ctx->g.n_v)), dim3(NT), 0, ctx->stream, ctx->g.n_v, ctx->d_node_i, ctx->d_node_e, x, o);
@@ -5004,6 +5117,7 @@ int knp_profile_reset(knp_ctx* ctx) {
     ctx->n_fused_dots = 0;
     ctx->n_spmv_dots = 0;
     ctx->n_fused_tail = ctx->n_knod_skip = 0;
+    ctx->n_ahead_adopted = ctx->n_ahead_discarded = 0;
     return KNP_OK;
 }
 // Bytes the kernels of one application must move, from the sizes of the arrays they read and write (the "algorithmic bytes" of the
@@ -5085,6 +5199,8 @@ int knp_get_stats(const knp_ctx* ctx, double* out) {
     out[KNP_ST_SPMV_DOTS] = (double)ctx->n_spmv_dots;
     out[KNP_ST_FUSED_TAILS] = (double)ctx->n_fused_tail;
     out[KNP_ST_KNOD_SKIPS] = (double)ctx->n_knod_skip;
+    out[KNP_ST_AHEAD_ADOPTED] = (double)ctx->n_ahead_adopted;
+    out[KNP_ST_AHEAD_DISCARDED] = (double)ctx->n_ahead_discarded;
     return KNP_OK;
 }
 int knp_get_launch_info(const knp_ctx* ctx, int32_t* out, int n) {

@@ -264,6 +264,7 @@ static int krylov_begin(knp_ctx* ctx, const double* b, double* x, int32_t max_it
         return KNP_E_ARG;
     }
     ctx->fields_current = ctx->knod_current = false;   // x is about to change
+    KCHK(drop_ahead(ctx));
     KCHK(ensure_work(ctx, restart));
     if (flexible && ctx->pc_kind != KNP_PC_NONE) KCHK(ensure_z(ctx, restart));   // with no preconditioner Z is V: nothing is allocated or copied
     prof_collect_ready(ctx);
@@ -575,6 +576,7 @@ int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doubl
                 ctx->fields_current = true;
                 ctx->knod_current = ctx->asm_dmax > 0;
                 ++ctx->n_fused_tail;
+                KCHK(speculate_asm(ctx));   // the next step's matrix, behind this kernel on the assembly stream
             } else {
                 krylov_update_plain(K, jd, ctx->d_V, x);
             }
