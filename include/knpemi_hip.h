@@ -753,6 +753,50 @@ enum { KNP_AI_A_LANES = 0, KNP_AI_P_LANES = 1, KNP_AI_R_LANES = 2, KNP_AI_S_LANE
        KNP_AI_COUNT = 23 };
 int knp_amg_get_level_info(const knp_ctx* ctx, int32_t hier, int32_t level, int32_t* out /* host [n] */, int n);
 
+/* ---- mesh refinement (csrc/knp_refine.inc; cgx_hip/refine.py) ----------------------------------------------------------------
+ * Uniform red refinement of P1 triangles / tetrahedra and the transfer of nodal fields to the refined mesh.  The mesh is refined
+ * before a context exists: these entry points take no knp_ctx.  Every pointer is DEVICE memory, every launch goes to `stream`
+ * (a hipStream_t; NULL = the default stream), nothing is read back and nothing is synchronised.  KNP_E_ARG for a null pointer, a
+ * dimension other than 2 / 3 or a count outside [0, 2^31 - 1] (a fine count included; n_vertices >= 1: the keys then stay below 2^62);
+ * KNP_E_HIP when a launch fails.
+ *
+ * Numbering.  Coarse vertices keep 0 .. nv-1.  The unique edge (a, b), a < b, has the 64-bit key a*nv + b and gets the vertex
+ * nv + (rank of its key among the sorted unique keys) at (x[a] + x[b]) * 0.5 per component.  The caller sorts and deduplicates the
+ * keys between knp_refine_edge_keys and the other calls; the kernels find an edge by binary search in that array.
+ * Local edges of a cell in key order: 2D 01 02 12; 3D 01 02 03 12 13 23.  Below, 0..dim are the cell's vertices and m.. the midpoints.
+ *
+ * Children.  Cell c becomes the cells 2^dim c .. 2^dim c + 2^dim - 1, each with the orientation of c (fixed tables, no determinant):
+ *   2D  (0 m01 m02) (m01 1 m12) (m02 m12 2) (m01 m12 m02)
+ *   3D  (0 m01 m02 m03) (m01 1 m12 m13) (m02 m12 2 m23) (m03 m13 m23 3), then four around the diagonal k of the inner octahedron:
+ *       k = 0, m01-m23: (m01 m23 m02 m03) (m01 m23 m03 m13) (m01 m23 m13 m12) (m01 m23 m12 m02)
+ *       k = 1, m02-m13: (m02 m13 m03 m01) (m02 m13 m23 m03) (m02 m13 m12 m23) (m02 m13 m01 m12)
+ *       k = 2, m03-m12: (m03 m12 m01 m02) (m03 m12 m02 m23) (m03 m12 m23 m13) (m03 m12 m13 m01)
+ * Diagonal rule.  For k = 0, 1, 2 with (p q r t) = (0 1 2 3), (0 2 1 3), (0 3 1 2): d = ((x_p + x_q) - x_r) - x_t per component,
+ * s_k = (d0*d0 + d1*d1) + d2*d2, every operation rounded on its own (no fused multiply-add).  k replaces the best so far only if
+ * s_k < (1 - 2^-30) * s_best: near-ties go to the earliest candidate.
+ * Tagged facets.  (a b) -> (a mab) (mab b); (a b c) -> (a mab mac) (mab b mbc) (mac mbc c) (mab mbc mac), children 2^(dim-1) f + j. */
+
+/* keys [n_items * n_edges] of the items' edges, n_edges = 1, 3, 6 for nodes_per_item = 2, 3, 4 (facets of 2D / cells of 2D or facets
+ * of 3D / cells of 3D).  An item with a vertex outside [0, nv) or with a vertex twice gets the keys 0 and sets *flag to 1 (flag is
+ * never cleared here). */
+int knp_refine_edge_keys(int32_t nodes_per_item, int64_t n_items, int64_t n_vertices, const int32_t* items, int64_t* keys, int32_t* flag,
+                         void* stream);
+/* fine_coords [(nv + n_edges) * dim]: the coarse coordinates, then the midpoints; edge_vertices [n_edges * 2] = (a, b) of every key */
+int knp_refine_vertices(int32_t dim, int64_t n_vertices, int64_t n_edges, const int64_t* unique_keys, const double* coords,
+                        double* fine_coords, int32_t* edge_vertices, void* stream);
+/* fine_cells [n_cells * 2^dim * (dim+1)], fine_tags [n_cells * 2^dim] (the parent's tag), diagonal [n_cells] (dim 3; may be NULL in
+ * 2D).  Cells must have passed knp_refine_edge_keys; a cell with a vertex out of range writes nothing. */
+int knp_refine_cells(int32_t dim, int64_t n_cells, int64_t n_vertices, int64_t n_edges, const int64_t* unique_keys, const int32_t* cells,
+                     const int32_t* cell_tags, const double* coords, int32_t* fine_cells, int32_t* fine_tags, uint8_t* diagonal, void* stream);
+/* fine_facets [n_facets * 2^(dim-1) * dim], fine_values [n_facets * 2^(dim-1)].  A facet with a vertex out of range, a vertex twice
+ * or an edge whose key is not among unique_keys adds 1 to *n_missing and writes nothing. */
+int knp_refine_facets(int32_t dim, int64_t n_facets, int64_t n_vertices, int64_t n_edges, const int64_t* unique_keys, const int32_t* facets,
+                      const int32_t* values, int32_t* fine_facets, int32_t* fine_values, int32_t* n_missing, void* stream);
+/* n_fields nodal arrays at once, field f at in + f*ld_in (nv values) and out + f*ld_out (nv + n_edges values):
+ * out[:nv] = in, out[nv + e] = 0.5 * (in[a_e] + in[b_e]).  in and out must not overlap. */
+int knp_refine_prolong(int32_t n_fields, int64_t n_vertices, int64_t n_edges, const int32_t* edge_vertices, const double* in, int64_t ld_in,
+                       double* out, int64_t ld_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,6 +177,12 @@ SIGNATURES = {
     "knp_get_traffic_model": (C.c_int, [vp, f64p]),
     "knp_get_launch_info": (C.c_int, [vp, i32p, C.c_int]),
     "knp_amg_get_level_info": (C.c_int, [vp, C.c_int32, C.c_int32, i32p, C.c_int]),
+    # context-free: device pointers and a stream (cgx_hip/refine.py)
+    "knp_refine_edge_keys": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, vp, vp, vp, vp]),
+    "knp_refine_vertices": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, vp, vp, vp, vp, vp]),
+    "knp_refine_cells": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "knp_refine_facets": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp]),
+    "knp_refine_prolong": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, vp]),
 }
 
 _lib = None

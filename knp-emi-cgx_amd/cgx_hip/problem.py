@@ -314,6 +314,17 @@ class MixedDimensionalProblem(ABC):
     # ---------------------------------------------------------------- domain (:634-733)
     def setup_domain(self):
         self.print("Setting up mesh ...")
+        # config key ``refine_levels`` (top level, default 0): the mesh read below is refined that many times on the GPU before it is
+        # partitioned (cgx_hip/refine.py); every rank refines the whole mesh, as every rank loads it
+        self.refinement = None
+        n_refine = 0
+        if hasattr(self, "config") and self.config.get("refine_levels", 0) != 0:
+            from .refine import check_levels
+            n_refine = check_levels(self.config["refine_levels"])
+            if self.MMS_test:
+                raise ValueError("refine_levels with MMS_test: MMS meshes are generated at N_mesh")
+            if self._local_mesh_override is not None:
+                raise ValueError("refine_levels with a local_mesh override: the override is the mesh")
         if self._local_mesh_override is not None:
             lm = self._local_mesh_override
             self.mesh_description = lm.description
@@ -340,6 +351,12 @@ class MixedDimensionalProblem(ABC):
         else:
             coords, cells, cell_tags, facet_tags, desc = meshmod.load_mesh(
                 self.input_files["mesh_file"], self.input_files["facet_file"], self.mesh_conversion_factor)
+            if n_refine:
+                from .refine import refine
+                self.refinement = refine(coords, cells, cell_tags, facet_tags, n_refine)
+                coords, cells, cell_tags, facet_tags = (self.refinement.coords, self.refinement.cells, self.refinement.cell_tags,
+                                                        self.refinement.facet_tags)
+                desc += f", refined {n_refine}×"
             self.mesh_description = desc
             if np.all(np.array(self.intra_tags) < np.array(self.extra_tag).min()) or \
                np.all(np.array(self.intra_tags) > np.array(self.extra_tag).max()):

@@ -118,6 +118,58 @@ def _match_rows(reference_rows, rows):
     return np.where(hit, order[pos], -1)
 
 
+def write_mesh_and_tags(path, coords, cells, cell_tags, facets, facet_tags):
+    """Writes ``path`` (.xdmf) and its .h5 in the layout of ``dolfinx.io.XDMFFile.write_mesh`` + ``write_meshtags`` twice (the
+    reference's src/CGx/utils/refine_mesh.py:68-71): grid "mesh", and the tag grids "ct" / "ft" that list their own entities
+    (``/MeshTags/<name>/topology`` + ``/Values``) over the mesh's geometry.  ``facets`` / ``facet_tags`` may be None (no "ft" grid).
+    ``read_mesh_and_tags(path, path)`` returns the five arrays as they were passed."""
+    from .hdf5_write import Hdf5Writer
+    path = str(path)
+    if not path.endswith(".xdmf"):
+        raise XdmfError(f"{path}: the mesh file name must end in .xdmf")
+    coords = np.ascontiguousarray(coords, dtype=np.float64)
+    cells = np.ascontiguousarray(cells, dtype=np.int64)
+    cell_tags = np.ascontiguousarray(cell_tags, dtype=np.int32).reshape(-1, 1)
+    dim = cells.shape[1] - 1
+    if dim not in (2, 3) or coords.shape[1] != dim or len(cell_tags) != len(cells):
+        raise XdmfError(f"{path}: triangles or tetrahedra with one tag per cell and {dim}D points expected")
+    h5 = path[:-5] + ".h5"
+    base = os.path.basename(h5)
+    names = {2: "PolyLine", 3: "Triangle", 4: "Tetrahedron"}
+    geometry = [f'      <Geometry GeometryType="{"XY" if dim == 2 else "XYZ"}">',
+                f'        <DataItem Dimensions="{len(coords)} {dim}" NumberType="Float" Precision="8" Format="HDF">{base}:/Mesh/mesh/geometry</DataItem>',
+                '      </Geometry>']
+
+    def topology(n, nodes, where):
+        return [f'      <Topology TopologyType="{names[nodes]}" NumberOfElements="{n}" NodesPerElement="{nodes}">',
+                f'        <DataItem Dimensions="{n} {nodes}" NumberType="Int" Precision="8" Format="HDF">{base}:{where}</DataItem>',
+                '      </Topology>']
+
+    def tag_grid(name, n, nodes):
+        return [f'    <Grid Name="{name}" GridType="Uniform">'] + topology(n, nodes, f"/MeshTags/{name}/topology") + geometry + [
+            f'      <Attribute Name="{name}" AttributeType="Scalar" Center="Cell">',
+            f'        <DataItem Dimensions="{n} 1" NumberType="Int" Precision="4" Format="HDF">{base}:/MeshTags/{name}/Values</DataItem>',
+            '      </Attribute>', '    </Grid>']
+    body = ['    <Grid Name="mesh" GridType="Uniform">'] + topology(len(cells), dim + 1, "/Mesh/mesh/topology") + geometry + ['    </Grid>']
+    with Hdf5Writer(h5) as w:
+        w.write("/Mesh/mesh/geometry", coords)
+        w.write("/Mesh/mesh/topology", cells)
+        w.write("/MeshTags/ct/topology", cells)
+        w.write("/MeshTags/ct/Values", cell_tags)
+        body += tag_grid("ct", len(cells), dim + 1)
+        if facets is not None:
+            facets = np.ascontiguousarray(facets, dtype=np.int64).reshape(-1, dim)
+            fvals = np.ascontiguousarray(facet_tags, dtype=np.int32).reshape(-1, 1)
+            if len(fvals) != len(facets):
+                raise XdmfError(f"{path}: {len(fvals)} facet tags for {len(facets)} facets")
+            w.write("/MeshTags/ft/topology", facets)
+            w.write("/MeshTags/ft/Values", fvals)
+            body += tag_grid("ft", len(facets), dim)
+    with open(path, "w") as f:
+        f.write("\n".join(['<?xml version="1.0"?>', '<!DOCTYPE Xdmf SYSTEM "Xdmf.dtd" []>', '<Xdmf Version="3.0">', '  <Domain>']
+                          + body + ['  </Domain>', '</Xdmf>', '']))
+
+
 def read_mesh_and_tags(mesh_file, facet_file, ct_name=None, ft_name=None):
     """Returns (coords (n_v, dim), cells (n_c, dim+1) int32, cell_tags (n_c,) int32, (facet_vertices, facet_values) or None).
 

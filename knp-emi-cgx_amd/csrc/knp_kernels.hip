@@ -5280,3 +5280,6 @@ int knp_amg_get_level_info(const knp_ctx* ctx, int32_t hier, int32_t level, int3
 #include "knp_membrane_functional.inc"
 // derived fields: the value of a functional's program per cell / facet, and its measure-weighted average onto the vertices
 #include "knp_fields.inc"
+
+// mesh refinement before a context exists: edge keys, midpoints, child cells and facets, prolongation of nodal fields (knp_refine_*)
+#include "knp_refine.inc"
