@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "knp_step_state.hpp"
 #include "knpemi_hip.h"
 
 #define KNP_NPROF 5
@@ -458,42 +459,21 @@ struct knp_ctx {
     int64_t n_spmv_dots = 0;    // reductions whose first stage ran in the SpMV on A (KNP_SPMV_DOTS, flexible GMRES)
     // Fused tail of a solve (k_lincomb_unpack: the last x += V y of knp_gmres_solve also unpacks x into the registered fields and
     // writes the node-indexed concentrations d_knod).  `tail_ok`: every unknown is reached through node_i / node_e exactly once and
-    // there are no ghost nodes (knp_create).  `fields_current`: the registered fields equal unpack(tail_x); `knod_current`: d_knod
-    // holds the concentrations of tail_x.  Both are CLEARED by every entry that writes x or could make the fields or d_knod stale:
-    //   knp_gmres_solve, knp_fgmres_solve (krylov_begin), knp_project_nullspace, knp_pack, knp_set_unpack_target, knp_set_dirichlet,
-    //   knp_pc_setup, knp_assemble_precond (rewrites d_knod from its own fields), a knp_unpack that runs k_unpack, and the matrix
-    //   assembly itself (knod_current and the caller's promise are consumed there).
-    // `fields_promise`: knp_fields_unchanged -- the caller vouches that nobody wrote the concentration fields since the last
-    // knp_unpack; one shot, consumed by the next matrix assembly.
+    // there are no ghost nodes (knp_create).
     int fused_tail = 1;       // KNP_FUSED_TAIL=0: off (read at knp_pc_setup)
     int update_early = 1;     // k_update_scale returns early on the converging iteration (KNP_UPDATE_EARLY=0: off, read at knp_pc_setup)
     bool tail_ok = false;
     bool have_tail_target = false;
     knp_fields_out tail_target = {};
-    const double* tail_x = nullptr;
-    bool fields_current = false, knod_current = false, fields_promise = false;
-    bool knod_skipped = false;       // the last matrix assembly skipped k_nodal_conc (knp_get_traffic_model)
-    int64_t n_fused_tail = 0;        // solves that ended in k_lincomb_unpack
-    int64_t n_knod_skip = 0;         // matrix assemblies that skipped k_nodal_conc
     // Matrix assembly ahead of the caller (KNP_ASM_AHEAD; speculate_asm, adopt_ahead): a solve that ended in k_lincomb_unpack enqueues
     // the next step's time-dependent assembly on stream_asm, into the ALTERNATE buffers d_at_alt / d_ax_alt, so that A of the step just
-    // solved stays readable.  The next knp_assemble_matrix(_async) adopts it (swaps the buffers, launches nothing) iff the caller gave
-    // the promise and passes the recorded pointers with the recorded dt; otherwise it is discarded.  `asm_armed`: the last matrix
-    // assembly, normal or adopted, took the skip path, i.e. the caller leaves the fields alone between unpack and assembly; cleared by
-    // every discard, so a caller that writes the fields pays one wasted assembly each time the pattern breaks.  A pending speculation is
-    // DROPPED (drop_ahead: joined, counted as discarded) by every entry that clears knod_current above and by knp_set_params.
+    // solved stays readable.  The next knp_assemble_matrix(_async) adopts it (swaps the buffers, launches nothing) or it is discarded.
     int asm_ahead = 1;               // KNP_ASM_AHEAD (read at knp_pc_setup): 0 off, 1 where both copies fit the Infinity Cache next to the SpMV's streams, 2 always
-    bool asm_armed = false;
     bool asm_alt_failed = false;     // the alternate buffers could not be allocated: this context never assembles ahead
     double *d_at_alt = nullptr, *d_ax_alt = nullptr;   // allocated (NaN-filled) at the first speculation
-    struct AsmAhead {
-        bool pending = false;
-        const double* k_i[3] = {nullptr, nullptr, nullptr};
-        const double* k_e[3] = {nullptr, nullptr, nullptr};
-        const double* phi_m = nullptr;
-        double dt = 0.0;
-    } ahead;
-    int64_t n_ahead_adopted = 0, n_ahead_discarded = 0;
+    // What the tail left current, the caller's promise, the pending speculation and their counters: one protocol, whose events and
+    // rules are in knp_step_state.hpp
+    KnpStepState step;
     // step timers (knp_timer_mark / knp_timer_read): timing events recorded on the main stream, read back in one go
     std::vector<hipEvent_t> tm_events;
     size_t tm_used = 0;
@@ -521,6 +501,24 @@ struct knp_ctx {
     std::vector<ProfRec> prof_recs;
     double prof_ms[KNP_NPROF] = {0, 0, 0, 0, 0};
     int64_t prof_n[KNP_NPROF] = {0, 0, 0, 0, 0};
+};
+
+// One GPU and nothing to exchange: no halo hook, no all-reduce hook, no level hook, no peer-to-peer plans.  The paths that reach across
+// the step boundary are built for such contexts; what each of them asks beyond this stands at its site.
+static inline bool exchange_free(const knp_ctx* ctx) { return !ctx->halo && !ctx->allreduce && !ctx->level_comm && !ctx->p2p; }
+// kernel classes beyond the SpMV's (bit 0, timed by events of its own) are being timed: paths that skip, fuse or move launches stand back
+static inline bool class_timing(const knp_ctx* ctx) { return (ctx->prof_on & ~1) != 0; }
+
+// "The launches of this scope go to that stream": every launcher takes ctx->stream, so work is moved by swapping it.  The destructor
+// puts the stream back on every way out, an early return included.
+struct StreamScope {
+    StreamScope(knp_ctx* ctx, hipStream_t s) : ctx_(ctx), saved_(ctx->stream) { ctx_->stream = s; }
+    ~StreamScope() { ctx_->stream = saved_; }
+    StreamScope(const StreamScope&) = delete;
+    StreamScope& operator=(const StreamScope&) = delete;
+private:
+    knp_ctx* ctx_;
+    hipStream_t saved_;
 };
 
 // Threads of the host-side OpenMP loops: the CPU share of the process, not the machine.  A GPU box shows all logical CPUs of its host

@@ -71,7 +71,7 @@ static void side_discard(knp_ctx* ctx);
 static DevParams make_params(const knp_ctx* ctx);
 static int64_t phi_block_nnz(const knp_ctx* ctx);
 static int join_asm(knp_ctx* ctx);
-static int drop_ahead(knp_ctx* ctx);
+static int drop_ahead(knp_ctx* ctx, bool dropped);
 static int speculate_asm(knp_ctx* ctx);
 static bool fin_ok(const knp_ctx* ctx);
 static hipEvent_t prof_event(knp_ctx* ctx);
@@ -452,17 +452,10 @@ k_assemble_nodes_tr(int n_nodes, DevParams P, int cmax, const int32_t* __restric
 }
 
 // what the volume assembly reads the previous concentrations from: the node-indexed copy (fused cell means) or the per-cell means
-// `matrix`: the matrix assembly, which may find d_knod already written by the tail of the last solve (k_lincomb_unpack) -- skipped
-// iff the caller promised that the fields were not written since (knp_fields_unchanged) AND knod_current AND these are the
-// concentration fields the tail unpacked into.  Promise and knod_current are consumed here whatever the outcome.
-static void launch_cell_means(knp_ctx* ctx, const FieldPtrs& f, bool matrix = false) {
+// (the matrix assembly may find d_knod already written by the tail of the last solve: its entry has asked begin_assembly, and does
+// not come here then)
+static void launch_cell_means(knp_ctx* ctx, const FieldPtrs& f) {
     const KnpHostGraph& g = ctx->g;
-    bool skip = matrix && ctx->asm_dmax > 0 && ctx->fields_promise && ctx->knod_current && ctx->have_tail_target && (ctx->prof_on & ~1) == 0;
-    for (int j = 0; j < 3 && skip; ++j) skip = f.ki[j] == ctx->tail_target.k_i[j] && f.ke[j] == ctx->tail_target.k_e[j];
-    ctx->fields_promise = false;
-    ctx->knod_current = false;
-    if (matrix) ctx->knod_skipped = skip;
-    if (skip) { ++ctx->n_knod_skip; ctx->asm_armed = true; return; }   // (armed: the next solve's tail may assemble ahead)
     if (ctx->asm_dmax > 0)
         hipLaunchKernelGGL(k_nodal_conc, dim3(nblocks(g.n_nodes)), dim3(NT), 0, ctx->stream, g.n_nodes, ctx->d_node_vertex, ctx->d_node_side, f, ctx->d_knod);
     else
@@ -1710,6 +1703,8 @@ k_spmv_node_dots(int n_list, const int32_t* __restrict__ pair_ptr, const int32_t
 static bool launch_spmv_dots(knp_ctx* ctx, const double* x, const double* b, double* y, int m, int64_t ldv, const double* V, int* nb_out) {
     const int n_list = ctx->g.n_nodes_owned;
     const int G = ctx->spmv_group;
+    // (not exchange_free: only x's own exchanges matter to the product -- fin_ok has asked about the all-reduce hook, the level hook serves
+    // the preconditioner)
     if (!ctx->spmv_dots || !fin_ok(ctx) || ctx->halo || ctx->p2p || ctx->n_bc > 0 || ctx->d_pair_MK == nullptr || n_list <= 0 || m < 0 ||
         m > BU_MAX_M || clamp_lanes<4, 32>(G) != G)
         return false;
@@ -3233,7 +3228,7 @@ int knp_set_params(knp_ctx* ctx, double dt, double F, double C_M, double psi, in
     CHECK_CTX(ctx);
     if (n_ions != 3 || !z || !Di || !De) { ctx->err = "n_ions must be 3 (Na, K, Cl; KNPEMIx_problem.py:980-981)"; return KNP_E_ARG; }
     if (!(dt > 0) || !(psi > 0) || F == 0.0) { ctx->err = "dt, psi must be positive and F non-zero"; return KNP_E_ARG; }
-    KCHK(drop_ahead(ctx));   // assembled with the parameters as they were
+    KCHK(drop_ahead(ctx, ctx->step.inputs_changing()));   // assembled with the parameters as they were
     ctx->dt = dt; ctx->F = F; ctx->C_M = C_M; ctx->psi = psi; ctx->n_ions = 3;
     ctx->asm_dt = -1.0;   // constant blocks must be rewritten
     for (int j = 0; j < 3; ++j) {
@@ -3343,8 +3338,7 @@ int knp_set_dirichlet(knp_ctx* ctx, int32_t n, const int32_t* dofs) {
         ctx->n_bc = n;
     }
     ctx->asm_dt = -1.0;   // constant blocks of the touched rows must be rewritten if the set changes
-    ctx->fields_current = ctx->knod_current = false;
-    KCHK(drop_ahead(ctx));
+    KCHK(drop_ahead(ctx, ctx->step.x_changing()));
     return KNP_OK;
 }
 
@@ -3359,226 +3353,8 @@ int knp_set_sources(knp_ctx* ctx, const double* const* fi, const double* const* 
     return KNP_OK;
 }
 
-static int check_fields(knp_ctx* ctx, const knp_fields* f, bool need_phim) {
-    if (!f) { ctx->err = "null fields"; return KNP_E_ARG; }
-    for (int j = 0; j < 3; ++j)
-        if (!f->k_i[j] || !f->k_e[j]) { ctx->err = "null concentration field"; return KNP_E_ARG; }
-    if (need_phim && !f->phi_m) { ctx->err = "null phi_m field"; return KNP_E_ARG; }
-    if (!(ctx->dt > 0)) { ctx->err = "knp_set_params has not been called"; return KNP_E_STATE; }
-    return KNP_OK;
-}
-
-// cc = psi / (sum_j z_j^2 k_j) / M_lumped at every owned node (Schur term of the block-triangular preconditioner)
-// Only the block-triangular forms read cc (k_level_up MODE 1, k_schur_fin): skipped for the kinds that never do.  Before knp_pc_setup
-// (kind NONE) it is written, so that a block-triangular setup after the first assembly finds it.
-static void launch_schur_diag(knp_ctx* ctx, const FieldPtrs& f) {
-    if (ctx->pc_kind == KNP_PC_AMG || ctx->pc_kind == KNP_PC_VBJACOBI) { ctx->have_cc = false; return; }
-    const KnpHostGraph& g = ctx->g;
-    hipLaunchKernelGGL(k_schur_diag, dim3(nblocks(g.n_nodes_owned)), dim3(NT), 0, ctx->stream, g.n_nodes_owned, ctx->psi, ctx->z[0], ctx->z[1],
-                       ctx->z[2], ctx->d_node_vertex, ctx->d_node_side, f, ctx->d_ML, ctx->d_cc);
-    ctx->have_cc = true;
-}
-
-// join the matrix assembly that runs on its own stream (knp_assemble_matrix_async): everything that reads A, or writes what
-// that assembly reads or uses as scratch (the cell means, the facet matrices), calls this first
-static int join_asm(knp_ctx* ctx) {
-    if (ctx->asm_pending) {
-        HIPCHK(hipStreamWaitEvent(ctx->stream, ctx->ev_asm, 0));
-        ctx->asm_pending = false;
-    }
-    return KNP_OK;
-}
-
-// `at`, `ax`: where the solution-dependent entries go (ctx->d_at / d_ax, or the alternate pair of a speculative assembly, which is
-// the time-dependent form only and finds d_knod current: `knod_ready`)
-static int assemble_matrix_on_stream(knp_ctx* ctx, const knp_fields* fields, bool with_schur_diag, double* at, double* ax, bool knod_ready = false) {
-    const KnpHostGraph& g = ctx->g;
-    const DevParams P = make_params(ctx);
-    FieldPtrs f = make_fields(fields);
-    ProfScope ps(ctx, 3);
-    if (!knod_ready) launch_cell_means(ctx, f, true);
-    // The (k,k) and (phi,k) blocks do not depend on the previous solution (SURVEY 3.2 obs. 1): after the first
-    // assembly only the K[k_prev]-type and membrane entries are rewritten, unless KNP_ASM_FULL=1 asks for the
-    // reference's behaviour (A.zeroEntries() + full re-assembly, KNPEMIx_solver.py:110-115).
-    const bool td_only = ctx->have_A && !ctx->asm_full && ctx->asm_dt == ctx->dt;
-    if (td_only) launch_assemble_nodes<false, true>(ctx, P, at, ctx->d_ac);
-    else launch_assemble_nodes<false, false>(ctx, P, at, ctx->d_ac);
-    ctx->asm_dt = ctx->dt;
-    if (g.n_g > 0) {
-        if (g.dim == 2)
-            hipLaunchKernelGGL((k_gamma_facets<2, true, false, 8, 1, NT, 1>), dim3(nblocks((int64_t)g.n_g * 8)), dim3(NT), 0, ctx->stream, g.n_g, g.n_q, P,
-                               ctx->d_fv, ctx->d_fmeas, ctx->d_qp, ctx->d_qw, f, 0, ctx->d_coords, ctx->d_gamma_prog,
-                               (const int32_t* const*)nullptr, (const int32_t*)nullptr, (const double* const*)nullptr,
-                               (const int32_t*)nullptr, 0, 0, ctx->d_fmat, ctx->d_fvec);
-        else if (gamma_many(g)) {  // 4 lanes per facet: the 36 points exactly (see gamma_many)
-            // (matrix part: 9 points in flight per lane 0.76 ms on 1.5 M facets, 3 points 0.82, 1 point 0.95 -- unlike the mechanism currents)
-            hipLaunchKernelGGL((k_gamma_facets<3, true, false, 4, 9, 64, 1>), dim3((unsigned)(((int64_t)g.n_g * 4 + 63) / 64)), dim3(64), 0, ctx->stream, g.n_g, g.n_q, P,
-                               ctx->d_fv, ctx->d_fmeas, ctx->d_qp, ctx->d_qw, f, 0, ctx->d_coords, ctx->d_gamma_prog,
-                               (const int32_t* const*)nullptr, (const int32_t*)nullptr, (const double* const*)nullptr,
-                               (const int32_t*)nullptr, 0, 0, ctx->d_fmat, ctx->d_fvec);
-        }
-        else
-            hipLaunchKernelGGL((k_gamma_facets<3, true, false, 16, 3, 64, 2>), dim3((unsigned)(((int64_t)g.n_g * 16 + 63) / 64)), dim3(64), 0, ctx->stream, g.n_g, g.n_q, P,
-                               ctx->d_fv, ctx->d_fmeas, ctx->d_qp, ctx->d_qw, f, 0, ctx->d_coords, ctx->d_gamma_prog,
-                               (const int32_t* const*)nullptr, (const int32_t*)nullptr, (const double* const*)nullptr,
-                               (const int32_t*)nullptr, 0, 0, ctx->d_fmat, ctx->d_fvec);
-        if (ctx->n_gp)
-            hipLaunchKernelGGL((k_gamma_pairs<false>), dim3(nblocks(ctx->n_gp)), dim3(NT), 0, ctx->stream, ctx->n_gp, g.n_g, g.dim, P,
-                               ctx->d_grow, ctx->d_gptr, ctx->d_gv_node_i, ctx->d_gv_node_e, ctx->d_gq_i, ctx->d_gq_e,
-                               ctx->d_gcptr, ctx->d_gc_facet, ctx->d_gc_lab, ctx->d_fmeas, ctx->d_fmat, ctx->d_pair_ptr,
-                               at, ax);
-    }
-    if (ctx->n_bc > 0)
-        hipLaunchKernelGGL(k_dirichlet_rows_A, dim3(nblocks(ctx->n_bc)), dim3(NT), 0, ctx->stream, ctx->n_bc, ctx->d_bc_dofs, ctx->d_pair_ptr,
-                           ctx->d_pair_col, ctx->d_node_gv, ctx->d_node_side, ctx->d_gptr, ctx->d_ac, at, ax);
-    // The Schur diagonal depends on the fields only.  knp_assemble_rhs of the same step has already written it; while a
-    // side-stream preconditioner application (knp_gmres_prepare) is in flight it READS d_cc, so it must not be rewritten here
-    // (nor by the asynchronous form, which runs next to the right-hand side assembly that writes it).
-    if (with_schur_diag && !ctx->prep.left()) launch_schur_diag(ctx, f);
-    HIPCHK(hipGetLastError());
-    ctx->have_A = true;
-    if (ctx->pc_kind == KNP_PC_VBJACOBI) {
-        hipLaunchKernelGGL(k_vbj_extract, dim3(nblocks(g.n_nodes_owned)), dim3(NT), 0, ctx->stream, g.n_nodes_owned,
-                           ctx->d_pair_ptr, ctx->d_pair_col, ctx->d_ac, at, ax, ctx->d_node_gv, ctx->d_node_side,
-                           ctx->d_gdiag, ctx->d_vbj);
-        HIPCHK(hipGetLastError());
-    }
-    return KNP_OK;
-}
-
-// ---- matrix assembly ahead of the caller (KNP_ASM_AHEAD) ----
-// The form that may run ahead, and be adopted: the time-dependent entries only, no Dirichlet rows, one GPU without hooks or
-// peer-to-peer plans, an AMG preconditioner (vertex-block Jacobi consumes A at assembly time), no kernel-class timing beyond the SpMV's.
-static bool ahead_form_ok(const knp_ctx* ctx) {
-    return ctx->asm_ahead && ctx->have_A && !ctx->asm_full && ctx->asm_dt == ctx->dt && ctx->n_bc == 0 && !ctx->halo && !ctx->allreduce &&
-           !ctx->level_comm && !ctx->p2p && (ctx->pc_kind == KNP_PC_AMG || ctx->pc_kind == KNP_PC_AMG_BT || ctx->pc_kind == KNP_PC_AMG_LT) &&
-           (ctx->prof_on & ~1) == 0;
-}
-static bool asm_async_off() {   // KNP_ASM_ASYNC=0: no assembly on a stream of its own, asked for or ahead
-    static const bool off = getenv("KNP_ASM_ASYNC") && atoi(getenv("KNP_ASM_ASYNC")) == 0;
-    return off;
-}
-static int ensure_asm_stream(knp_ctx* ctx) {
-    if (!ctx->stream_asm) {
-        HIPCHK(hipStreamCreateWithFlags(&ctx->stream_asm, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&ctx->ev_fork_asm, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&ctx->ev_asm, hipEventDisableTiming));
-    }
-    return KNP_OK;
-}
-// a pending speculative assembly whose inputs are about to change, or that nobody can use: joined (its kernels read the fields and
-// d_knod and use the facet matrices as scratch), counted, and the context disarmed
-static int drop_ahead(knp_ctx* ctx) {
-    if (!ctx->ahead.pending) return KNP_OK;
-    ctx->ahead.pending = false;
-    ctx->asm_armed = false;
-    ++ctx->n_ahead_discarded;
-    return join_asm(ctx);
-}
-// Called by knp_gmres_solve right behind k_lincomb_unpack, which has left the fields of the registered target and d_knod as the next
-// matrix assembly reads them: that assembly goes to the assembly stream now, into the alternate buffers (A of this step stays where
-// every reader finds it).  Nothing here waits; the first call allocates the alternate buffers.
-static int speculate_asm(knp_ctx* ctx) {
-    if (!ctx->asm_armed || !ahead_form_ok(ctx) || !ctx->knod_current || !ctx->have_tail_target || ctx->asm_pending || ctx->ahead.pending ||
-        ctx->prep.left() || ctx->asm_alt_failed || asm_async_off())
-        return KNP_OK;
-    // Two copies of the solution-dependent entries alternate from step to step.  Where the SpMV's streams (52 B per node pair) and
-    // the second copy (32 B per pair, 64 B per membrane vertex pair) do not fit the 256 MiB Infinity Cache together, the assembly
-    // into the other copy can evict what the next solve reads, and the host hole it fills is a fixed ~10 us: 512^2 (155 MB) gains,
-    // cube 64^3 (344 MB) showed no gain -- 7 of 8 alternated pairs 2-20 us slower in three jobs, level in a fourth (DESIGN section
-    // 3) -- so such contexts keep assembling when asked, and allocate no second buffer.  KNP_ASM_AHEAD=2 lifts the bound.
-    if (ctx->asm_ahead < 2 && 84.0 * (double)ctx->n_pairs + 128.0 * (double)ctx->n_gp > 256.0 * 1048576.0) return KNP_OK;
-    KCHK(ensure_asm_stream(ctx));
-    if (!ctx->d_at_alt) {
-        const size_t nat = (size_t)std::max<int64_t>(4 * ctx->n_pairs, 2) * sizeof(double), nax = (size_t)std::max<int64_t>(8 * ctx->n_gp, 2) * sizeof(double);
-        if (hipMalloc((void**)&ctx->d_at_alt, nat) != hipSuccess || hipMalloc((void**)&ctx->d_ax_alt, nax) != hipSuccess) {
-            (void)hipGetLastError();   // no room for a second buffer: this context assembles when asked, as before
-            dev_free(ctx->d_at_alt); dev_free(ctx->d_ax_alt);
-            ctx->asm_alt_failed = true;
-            return KNP_OK;
-        }
-        // NaN (all bits set) wherever the assembly does not write
-        HIPCHK(hipMemsetAsync(ctx->d_at_alt, 0xff, nat, ctx->stream_asm));
-        HIPCHK(hipMemsetAsync(ctx->d_ax_alt, 0xff, nax, ctx->stream_asm));
-    }
-    knp_fields f = {};
-    for (int j = 0; j < 3; ++j) { f.k_i[j] = ctx->tail_target.k_i[j]; f.k_e[j] = ctx->tail_target.k_e[j]; }
-    f.phi_m = ctx->tail_target.phi_m;
-    HIPCHK(hipEventRecord(ctx->ev_fork_asm, ctx->stream));
-    HIPCHK(hipStreamWaitEvent(ctx->stream_asm, ctx->ev_fork_asm, 0));
-    hipStream_t main_stream = ctx->stream;
-    ctx->stream = ctx->stream_asm;
-    const int rc = assemble_matrix_on_stream(ctx, &f, false, ctx->d_at_alt, ctx->d_ax_alt, true);
-    ctx->stream = main_stream;
-    KCHK(rc);
-    HIPCHK(hipEventRecord(ctx->ev_asm, ctx->stream_asm));
-    ctx->asm_pending = true;
-    ctx->ahead.pending = true;
-    for (int j = 0; j < 3; ++j) { ctx->ahead.k_i[j] = f.k_i[j]; ctx->ahead.k_e[j] = f.k_e[j]; }
-    ctx->ahead.phi_m = f.phi_m;
-    ctx->ahead.dt = ctx->dt;
-    return KNP_OK;
-}
-// At the top of a matrix assembly: take the speculative result if it is the assembly asked for -- the caller's promise, the recorded
-// pointers and dt, the form still eligible -- by swapping the buffers; nothing is launched and asm_pending stays as it is (the next
-// reader of A joins).  Otherwise the speculation is dropped and the caller's assembly runs as ever.
-static int adopt_ahead(knp_ctx* ctx, const knp_fields* fields, bool* adopted) {
-    *adopted = false;
-    if (!ctx->ahead.pending) return KNP_OK;
-    bool ok = ctx->fields_promise && ctx->knod_current && ahead_form_ok(ctx) && ctx->ahead.dt == ctx->dt && fields->phi_m == ctx->ahead.phi_m;
-    for (int j = 0; j < 3 && ok; ++j) ok = fields->k_i[j] == ctx->ahead.k_i[j] && fields->k_e[j] == ctx->ahead.k_e[j];
-    if (!ok) return drop_ahead(ctx);
-    std::swap(ctx->d_at, ctx->d_at_alt);
-    std::swap(ctx->d_ax, ctx->d_ax_alt);
-    ctx->ahead.pending = false;
-    ctx->fields_promise = false;
-    ctx->knod_current = false;
-    ctx->knod_skipped = true;   // counted here, where the caller's assembly is: the copy pass it would have run is the one skipped
-    ++ctx->n_knod_skip;
-    ++ctx->n_ahead_adopted;
-    *adopted = true;
-    return KNP_OK;
-}
-
-int knp_assemble_matrix(knp_ctx* ctx, const knp_fields* fields) {
-    CHECK_CTX(ctx);
-    KCHK(check_fields(ctx, fields, false));
-    bool adopted = false;
-    KCHK(adopt_ahead(ctx, fields, &adopted));
-    KCHK(join_asm(ctx));
-    if (adopted) {   // the in-line form also refreshes the Schur diagonal (see assemble_matrix_on_stream)
-        if (!ctx->prep.left()) launch_schur_diag(ctx, make_fields(fields));
-        HIPCHK(hipGetLastError());
-        return KNP_OK;
-    }
-    return assemble_matrix_on_stream(ctx, fields, true, ctx->d_at, ctx->d_ax);
-}
-
-// The same assembly on the library's own stream: it depends on the previous solution only, not on the gating update or the
-// right-hand side of the step, so the caller may enqueue the right-hand side chain (and knp_gmres_prepare) on the main stream
-// while it runs.  Every later call that needs A joins it (join_asm).  Falls back to the in-line form where the matrix is consumed
-// at once (vertex-block Jacobi extracts its blocks) or every kernel class is being timed.
-int knp_assemble_matrix_async(knp_ctx* ctx, const knp_fields* fields) {
-    CHECK_CTX(ctx);
-    KCHK(check_fields(ctx, fields, false));
-    bool adopted = false;
-    KCHK(adopt_ahead(ctx, fields, &adopted));
-    if (adopted) return KNP_OK;   // already on the assembly stream, since the end of the last solve
-    KCHK(join_asm(ctx));
-    if (asm_async_off() || ctx->pc_kind == KNP_PC_VBJACOBI || (ctx->prof_on & ~1) || !ctx->have_A || ctx->prep.left())
-        return assemble_matrix_on_stream(ctx, fields, true, ctx->d_at, ctx->d_ax);
-    KCHK(ensure_asm_stream(ctx));
-    HIPCHK(hipEventRecord(ctx->ev_fork_asm, ctx->stream));            // after everything that wrote the fields (unpack)
-    HIPCHK(hipStreamWaitEvent(ctx->stream_asm, ctx->ev_fork_asm, 0));
-    hipStream_t main_stream = ctx->stream;
-    ctx->stream = ctx->stream_asm;
-    const int rc = assemble_matrix_on_stream(ctx, fields, false, ctx->d_at, ctx->d_ax);
-    ctx->stream = main_stream;
-    KCHK(rc);
-    HIPCHK(hipEventRecord(ctx->ev_asm, ctx->stream_asm));
-    ctx->asm_pending = true;
-    return KNP_OK;
-}
+// ---- assembly entry points: matrix (in line, on its own stream, ahead of the caller), preconditioner matrix, right-hand side ----
+#include "knp_assembly.inc"
 
 // Form of the potential block of P.  0 (default): the reference's block-Jacobi form, - (C_M/F) M_Gamma on each side, sides uncoupled
 // (KNPEMIx_problem.py:735-738).  1: the potential block of A itself at assembly time, + (C_M/F) M_Gamma and the phi_i-phi_e
@@ -3631,105 +3407,6 @@ int knp_get_precond_phi_csr(const knp_ctx* cctx, int32_t* rp, int32_t* ci, doubl
         }
     }
     rp[g.n_nodes_owned] = (int32_t)k;
-    return KNP_OK;
-}
-
-int knp_assemble_precond(knp_ctx* ctx, const knp_fields* fields) {
-    CHECK_CTX(ctx);
-    side_discard(ctx);
-    KCHK(drop_ahead(ctx));   // d_knod is rewritten below
-    KCHK(join_asm(ctx));
-    KCHK(check_fields(ctx, fields, false));
-    const KnpHostGraph& g = ctx->g;
-    const DevParams P = make_params(ctx);
-    FieldPtrs f = make_fields(fields);
-    ProfScope ps(ctx, 3);
-    launch_cell_means(ctx, f);
-    launch_assemble_nodes<true, false>(ctx, P, ctx->d_p_vals, nullptr);
-    if (g.n_g > 0 && ctx->n_gp)
-        hipLaunchKernelGGL((k_gamma_pairs<true>), dim3(nblocks(ctx->n_gp)), dim3(NT), 0, ctx->stream, ctx->n_gp, g.n_g, g.dim, P,
-                           ctx->d_grow, ctx->d_gptr, ctx->d_gv_node_i, ctx->d_gv_node_e, ctx->d_gq_i, ctx->d_gq_e,
-                           ctx->d_gcptr, ctx->d_gc_facet, ctx->d_gc_lab, ctx->d_fmeas, ctx->d_fmat, ctx->d_pair_ptr,
-                           ctx->d_p_vals, nullptr, ctx->pc_coupled_phi ? ctx->d_px : nullptr);
-    if (ctx->n_bc > 0)
-        hipLaunchKernelGGL(k_dirichlet_rows_P, dim3(nblocks(ctx->n_bc)), dim3(NT), 0, ctx->stream, ctx->n_bc, ctx->d_bc_dofs, ctx->d_pair_ptr,
-                           ctx->d_pair_col, ctx->d_p_vals);
-    HIPCHK(hipGetLastError());
-    ctx->have_P = true;
-    return KNP_OK;
-}
-
-int knp_assemble_rhs(knp_ctx* ctx, const knp_fields* fields, double* b) {
-    CHECK_CTX(ctx);
-    side_discard(ctx);
-    KCHK(check_fields(ctx, fields, true));
-    if (!b) { ctx->err = "null b"; return KNP_E_ARG; }
-    const KnpHostGraph& g = ctx->g;
-    const DevParams P = make_params(ctx);
-    FieldPtrs f = make_fields(fields);
-    int n_aux = 0;
-    for (int k = 0; k < KNP_MAX_AUX; ++k)
-        if (fields->aux[k]) n_aux = k + 1;
-    for (int k = 0; k < n_aux; ++k)
-        if (!fields->aux[k]) { ctx->err = "aux fields must be contiguous from index 0"; return KNP_E_ARG; }
-    if (g.n_g > 0) {
-        KCHK(sync_program_table(ctx));
-        // every facet's program must exist
-        if ((int)ctx->progs.size() <= ctx->max_prog) { ctx->err = "a membrane facet refers to a program that was not set (knp_set_program)"; return KNP_E_STATE; }
-        for (int i = 0; i <= ctx->max_prog; ++i)
-            if (!ctx->progs[i].d_code) { ctx->err = "membrane program " + std::to_string(i) + " not set"; return KNP_E_STATE; }
-    }
-    ProfScope ps(ctx, 3);
-    if (g.n_g > 0) {
-        // dynamic LDS: register file [n_regs][NT] | constants | code of the block's program
-        const int n_regs = std::max(ctx->prog_regs, 1), ccap = (std::max(ctx->prog_consts_cap, 1) + 1) & ~1;   // even: code stays 16-B aligned
-#define GF_LAUNCH(D, L, Q, B, O)                                                                                              \
-    do {                                                                                                                      \
-        const size_t lds = ((size_t)n_regs * Q * B + ccap) * sizeof(double) + (size_t)4 * std::max(ctx->prog_len_cap, 1) * sizeof(int32_t); \
-        if (lds > 160 * 1024) { ctx->err = "membrane programs need more LDS than a CU has"; return KNP_E_STATE; }             \
-        if (lds != ctx->gamma_lds_set)                                                                                        \
-            HIPCHK(hipFuncSetAttribute((const void*)k_gamma_facets<D, false, true, L, Q, B, O>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        ctx->gamma_lds_set = lds;                                                                                             \
-        hipLaunchKernelGGL((k_gamma_facets<D, false, true, L, Q, B, O>), dim3((unsigned)(((int64_t)g.n_g * L + B - 1) / B)), dim3(B), lds, \
-                           ctx->stream, g.n_g, g.n_q, P, ctx->d_fv, ctx->d_fmeas, ctx->d_qp, ctx->d_qw, f, n_aux, ctx->d_coords,  \
-                           ctx->d_gamma_prog, (const int32_t* const*)ctx->d_prog_code, (const int32_t*)ctx->d_prog_len,         \
-                           (const double* const*)ctx->d_prog_consts, (const int32_t*)ctx->d_prog_nconsts, n_regs, ccap,        \
-                           ctx->d_fmat, ctx->d_fvec);                                                                          \
-    } while (0)
-        // measured on MI355X (cube64: 12 288 facets x 36 points; square512: 1 024 facets x 6 points): 3 points per lane and 16
-        // lanes per facet in 3D (258 -> 170 us vs one point per lane), one point per lane in 2D
-        void* jit = ctx->jit_fn[g.dim == 2 ? 0 : 1];
-        const bool many = gamma_many(g) && ctx->jit_fn[2];
-        if (many) jit = ctx->jit_fn[2];
-        if (jit) {   // run-time compiled programs (knp_jit.cpp): same kernel source, native mechanism code, no LDS register file
-            int n_g = g.n_g, n_q = g.n_q, n_aux_ = n_aux, nr = 0, cc0 = 0;
-            DevParams Pp = P;
-            FieldPtrs ff = f;
-            const int32_t* fv = ctx->d_fv; const double* fmeas = ctx->d_fmeas; const double* qp = ctx->d_qp; const double* qw = ctx->d_qw;
-            const double* coords = ctx->d_coords; const int32_t* gp = ctx->d_gamma_prog;
-            const int32_t* const* pc = (const int32_t* const*)ctx->d_prog_code; const int32_t* pl = ctx->d_prog_len;
-            const double* const* pk = (const double* const*)ctx->d_prog_consts; const int32_t* pn = ctx->d_prog_nconsts;
-            double* fmat = ctx->d_fmat; double* fvec = ctx->d_fvec;
-            void* args[] = {&n_g, &n_q, &Pp, &fv, &fmeas, &qp, &qw, &ff, &n_aux_, &coords, &gp, &pc, &pl, &pk, &pn, &nr, &cc0, &fmat, &fvec};
-            const int L = g.dim == 2 ? 8 : many ? 4 : 16;
-            HIPCHK(hipModuleLaunchKernel((hipFunction_t)jit, (unsigned)(((int64_t)g.n_g * L + 63) / 64), 1, 1, 64, 1, 1, 0, ctx->stream, args, nullptr));
-        } else if (g.dim == 2) GF_LAUNCH(2, 8, 1, 64, 2);
-        else GF_LAUNCH(3, 16, 3, 64, 2);
-#undef GF_LAUNCH
-    }
-    FieldPtrs src;
-    for (int j = 0; j < 3; ++j) { src.ki[j] = ctx->src_i[j]; src.ke[j] = ctx->src_e[j]; }
-    src.phim = nullptr;
-    for (int k = 0; k < KNP_MAX_AUX; ++k) src.aux[k] = nullptr;
-    if (g.n_nodes_owned > 0) {
-        with_lanes<4, 32>(ctx->pc_group, [&](auto G) {
-            hipLaunchKernelGGL((k_rhs<G()>), dim3(nblocks((int64_t)g.n_nodes_owned * G())), dim3(NT), 0, ctx->stream, g.n_nodes_owned, g.n_g, g.dim, ctx->dt,
-                               ctx->d_node_vertex, ctx->d_node_side, ctx->d_pair_ptr, ctx->d_pair_col, ctx->d_pair_M, f, src,
-                               ctx->have_sources ? 1 : 0, ctx->d_node_gv, ctx->d_gdiag, ctx->d_gcptr, ctx->d_gc_facet, ctx->d_gc_lab, ctx->d_fvec, b);
-        });
-    }
-    launch_schur_diag(ctx, f);   // before a possible knp_gmres_prepare forks the side stream (it reads d_cc)
-    HIPCHK(hipGetLastError());
     return KNP_OK;
 }
 
@@ -3838,8 +3515,7 @@ int knp_project_nullspace(knp_ctx* ctx, double* v) {
     CHECK_CTX(ctx);
     side_discard(ctx);
     if (!v) return KNP_E_ARG;
-    ctx->fields_current = ctx->knod_current = false;   // v may be the x the last solve unpacked
-    KCHK(drop_ahead(ctx));
+    KCHK(drop_ahead(ctx, ctx->step.x_changing()));   // v may be the x the last solve unpacked
     return project_ns(ctx, v);
 }
 
@@ -3882,11 +3558,10 @@ static int spmv_A(knp_ctx* ctx, double* x, const double* b, double* y, bool resi
         ++ctx->n_halo;
         HIPCHK(hipEventRecord(ctx->ev_x, ctx->stream));
         HIPCHK(hipStreamWaitEvent(ctx->stream3, ctx->ev_x, 0));
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream = ctx->stream3;
-        const int rc = knp_p2p_halo_forward(ctx, ctx->p2p_fine, x);
-        ctx->stream = main_stream;
-        KCHK(rc);
+        {
+            StreamScope on_halo(ctx, ctx->stream3);
+            KCHK(knp_p2p_halo_forward(ctx, ctx->p2p_fine, x));
+        }
         HIPCHK(hipEventRecord(ctx->ev_halo, ctx->stream3));
         if (residual) launch_spmv_node<1>(ctx, ctx->n_int, ctx->d_nodes_int, x, b, y, ea, nullptr);
         else launch_spmv_node<0>(ctx, ctx->n_int, ctx->d_nodes_int, x, b, y, ea, nullptr);
@@ -4492,9 +4167,10 @@ static double* amg_vcycle(knp_ctx* ctx, KnpAmgHier& H, int l, const double* b, d
             // the same overlap the SpMV on A has (same interior / boundary lists: P's graph is a subgraph of A's)
             (void)hipEventRecord(ctx->ev_x, ctx->stream);
             (void)hipStreamWaitEvent(ctx->stream3, ctx->ev_x, 0);
-            ctx->stream = ctx->stream3;
-            level_exchange(ctx, hidx, 0, 0, const_cast<double*>(b));
-            ctx->stream = st;
+            {
+                StreamScope on_halo(ctx, ctx->stream3);
+                level_exchange(ctx, hidx, 0, 0, const_cast<double*>(b));
+            }
             (void)hipEventRecord(ctx->ev_halo, ctx->stream3);
             down(ctx->n_int, ctx->d_nodes_int);
             (void)hipStreamWaitEvent(st, ctx->ev_halo, 0);
@@ -4567,6 +4243,7 @@ static bool fused_eligible(const knp_ctx* ctx, const KnpAmgHier& H) {
     const bool off = getenv("KNP_FUSED") && atoi(getenv("KNP_FUSED")) == 0;   // read at every knp_pc_setup
     if (off || !H.native0 || H.levels < 2 || H.cheby != 1 || H.pre != 1 || H.post != 1 || H.nc <= 0) return false;
     if (!(H.pt || H.pt_f || H.pt_phi || H.pt_phi_f || H.at0_rp)) return false;
+    // (not exchange_free: the all-reduce hook is not asked about -- the cycle reduces nothing across ranks, only its vectors' exchanges matter)
     if (ctx->level_comm || ctx->p2p || ctx->halo) return false;
     for (int l = 0; l < H.levels - 1; ++l) {
         const KnpAmgLevel& L = H.lv[l];
@@ -4754,8 +4431,7 @@ int knp_pc_setup(knp_ctx* ctx, int32_t kind) {
     ctx->fused_tail = !(getenv("KNP_FUSED_TAIL") && atoi(getenv("KNP_FUSED_TAIL")) == 0);
     ctx->update_early = !(getenv("KNP_UPDATE_EARLY") && atoi(getenv("KNP_UPDATE_EARLY")) == 0);
     ctx->asm_ahead = getenv("KNP_ASM_AHEAD") ? std::max(atoi(getenv("KNP_ASM_AHEAD")), 0) : 1;   // 0 off, 1 where it fits the cache, 2 always
-    ctx->fields_current = ctx->knod_current = false;
-    KCHK(drop_ahead(ctx));
+    KCHK(drop_ahead(ctx, ctx->step.x_changing()));
     for (int h = 0; h < KNP_MAX_HIER; ++h) ctx->hier[h].fused = 0;
     if (kind == KNP_PC_AMG) ctx->hier[0].fused = fused_eligible(ctx, ctx->hier[0]) ? 1 : 0;
     if (kind == KNP_PC_AMG_BT || kind == KNP_PC_AMG_LT) {   // both or none: the potential hierarchy then works on compact vectors
@@ -4981,8 +4657,7 @@ static bool same_target(const knp_ctx* ctx, const knp_fields_out* f) {
 }
 int knp_set_unpack_target(knp_ctx* ctx, const knp_fields_out* f) {
     CHECK_CTX(ctx);
-    ctx->fields_current = ctx->knod_current = ctx->fields_promise = false;
-    KCHK(drop_ahead(ctx));
+    KCHK(drop_ahead(ctx, ctx->step.target_changing()));
     ctx->have_tail_target = false;
     if (!f) return KNP_OK;
     OutPtrs o;
@@ -4993,7 +4668,7 @@ int knp_set_unpack_target(knp_ctx* ctx, const knp_fields_out* f) {
 }
 int knp_fields_unchanged(knp_ctx* ctx) {
     CHECK_CTX(ctx);
-    ctx->fields_promise = true;
+    ctx->step.promise();
     return KNP_OK;
 }
 int knp_get_nodal_conc(knp_ctx* ctx, double* out) {
@@ -5010,8 +4685,7 @@ int knp_pack(knp_ctx* ctx, const knp_fields_out* f, double* x) {
     if (!x) return KNP_E_ARG;
     OutPtrs o;
     KCHK(out_ptrs(ctx, f, o, false));
-    ctx->fields_current = ctx->knod_current = false;
-    KCHK(drop_ahead(ctx));
+    KCHK(drop_ahead(ctx, ctx->step.x_changing()));
     hipLaunchKernelGGL(k_pack, dim3(nblocks(ctx->g.n_nodes)), dim3(NT), 0, ctx->stream, ctx->g.n_nodes, ctx->d_node_vertex,
                        ctx->d_node_side, o, x);
     HIPCHK(hipGetLastError());
@@ -5022,9 +4696,8 @@ int knp_unpack(knp_ctx* ctx, const double* x, const knp_fields_out* f) {
     if (!x) return KNP_E_ARG;
     OutPtrs o;
     KCHK(out_ptrs(ctx, f, o, true));
-    if (ctx->fields_current && x == ctx->tail_x && same_target(ctx, f)) return KNP_OK;   // the solve's tail has written exactly this
-    ctx->fields_current = ctx->knod_current = false;
-    KCHK(drop_ahead(ctx));
+    if (ctx->step.unpack_is_current(x, same_target(ctx, f))) return KNP_OK;   // the solve's tail has written exactly this
+    KCHK(drop_ahead(ctx, ctx->step.x_changing()));
     KCHK(join_asm(ctx));   // the fields written here are what an assembly still in flight reads
     KCHK(halo_update(ctx, const_cast<double*>(x)));
     hipLaunchKernelGGL(k_unpack, dim3(nblocks(ctx->g.n_v)), dim3(NT), 0, ctx->stream, ctx->g.n_v, ctx->d_node_i, ctx->d_node_e, x, o);
@@ -5116,8 +4789,7 @@ int knp_profile_reset(knp_ctx* ctx) {
     ctx->n_allreduce = ctx->n_halo = ctx->n_readback = ctx->n_norm_fallback = 0;
     ctx->n_fused_dots = 0;
     ctx->n_spmv_dots = 0;
-    ctx->n_fused_tail = ctx->n_knod_skip = 0;
-    ctx->n_ahead_adopted = ctx->n_ahead_discarded = 0;
+    ctx->step.reset_counters();
     return KNP_OK;
 }
 // Bytes the kernels of one application must move, from the sizes of the arrays they read and write (the "algorithmic bytes" of the
@@ -5174,7 +4846,7 @@ int knp_get_traffic_model(const knp_ctx* ctx, double* out) {
     // the previous concentrations: node-indexed copy + one 32-byte record per neighbour + the byte table of the cells' vertices
     // (fused cell means), or the per-cell pass (connectivity, 3 (d+1) gathers, a 32-byte record written) + a record read per cell of a node
     // (the node-indexed copy pass -- 56 B per node -- only when the last matrix assembly ran it: the solve's tail may have written the copy)
-    const double conc = ctx->asm_dmax > 0 ? (ctx->knod_skipped ? 0.0 : (double)g.n_nodes * 56.0) + np_ * 36.0 + (double)ctx->n_node_cells * g.nv1
+    const double conc = ctx->asm_dmax > 0 ? (ctx->step.copy_pass_skipped() ? 0.0 : (double)g.n_nodes * 56.0) + np_ * 36.0 + (double)ctx->n_node_cells * g.nv1
                                           : (double)g.n_c * (4.0 * g.nv1 + 32.0 + 24.0 * g.nv1) + (double)ctx->n_node_cells * 36.0;
     out[2] = (double)(ctx->n_tc > 0 ? ctx->n_tc : ctx->n_contrib) * 9.0 + conc + np_ * 32.0 + ngp * (64.0 + 48.0);
     out[3] = no * (8.0 * 4.0 + 9.0) + np_ * (8.0 + 4.0 + 24.0) + (double)g.n_g * g.dim * 7.0 * 8.0 * 2.0;
@@ -5197,10 +4869,10 @@ int knp_get_stats(const knp_ctx* ctx, double* out) {
     out[KNP_ST_FUSED_LEVELS] = (double)nlf;
     out[KNP_ST_FUSED_DOTS] = (double)ctx->n_fused_dots;
     out[KNP_ST_SPMV_DOTS] = (double)ctx->n_spmv_dots;
-    out[KNP_ST_FUSED_TAILS] = (double)ctx->n_fused_tail;
-    out[KNP_ST_KNOD_SKIPS] = (double)ctx->n_knod_skip;
-    out[KNP_ST_AHEAD_ADOPTED] = (double)ctx->n_ahead_adopted;
-    out[KNP_ST_AHEAD_DISCARDED] = (double)ctx->n_ahead_discarded;
+    out[KNP_ST_FUSED_TAILS] = (double)ctx->step.fused_tails();
+    out[KNP_ST_KNOD_SKIPS] = (double)ctx->step.knod_skips();
+    out[KNP_ST_AHEAD_ADOPTED] = (double)ctx->step.ahead_adopted();
+    out[KNP_ST_AHEAD_DISCARDED] = (double)ctx->step.ahead_discarded();
     return KNP_OK;
 }
 int knp_get_launch_info(const knp_ctx* ctx, int32_t* out, int n) {

@@ -158,7 +158,8 @@ static void swap_side_ws(knp_ctx* ctx) {   // host-side pointer swap: kernel arg
 // vectors are exactly the per-level sets swapped above), gauge-projected norm from one reduction, pinned mirror for the result
 static bool side_concurrent_ok(const knp_ctx* ctx, int64_t cnt) {
     static const bool off = getenv("KNP_SIDE_CONCURRENT") && atoi(getenv("KNP_SIDE_CONCURRENT")) == 0;
-    if (off || ctx->halo || ctx->allreduce || ctx->level_comm || ctx->p2p || ctx->n_bc > 0 || !ctx->h_red_dev) return false;
+    // (deflation: fused_norm_possible asks below; class timing: knp_gmres_prepare, the only caller, has returned on it before it asks here)
+    if (off || !exchange_free(ctx) || ctx->n_bc > 0 || !ctx->h_red_dev) return false;
     if (!fused_norm_possible(ctx, cnt)) return false;
     if (ctx->pc_kind == KNP_PC_AMG) return ctx->hier[0].fused != 0;
     if (ctx->pc_kind == KNP_PC_AMG_BT || ctx->pc_kind == KNP_PC_AMG_LT) return ctx->hier[0].fused && ctx->hier[1].fused;
@@ -177,8 +178,8 @@ int knp_gmres_prepare(knp_ctx* ctx, const double* b) {
     // Distributed contexts: legal when EVERY exchange of the preconditioner runs in the library (native peer-to-peer plans):
     // those kernels are launched on ctx->stream, i.e. on the side stream here, in the same order on every rank, and the main
     // stream does no exchange until the solve joins.  With torch.distributed hooks (ordered on torch's stream) it stays a no-op.
-    if (off || ctx->gm_restart <= 0 || (ctx->prof_on & ~1)) return KNP_OK;
-    if ((ctx->halo || ctx->allreduce || ctx->level_comm || ctx->p2p) && !exchanges_all_native(ctx)) return KNP_OK;
+    if (off || ctx->gm_restart <= 0 || class_timing(ctx)) return KNP_OK;
+    if (!exchange_free(ctx) && !exchanges_all_native(ctx)) return KNP_OK;
     KCHK(ensure_side_stream(ctx));
     int rc = KNP_OK;
     const int64_t cnt = ctx->ns_on ? global_phi_count(ctx, &rc) : 0;
@@ -193,12 +194,11 @@ int knp_gmres_prepare(knp_ctx* ctx, const double* b) {
         return KNP_OK;
     }
     HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-    hipStream_t main_stream = ctx->stream;
-    ctx->stream = ctx->stream2;
     bool fused_norm = false;
-    rc = pc_apply_norm(ctx, b, ctx->d_w, cnt, &fused_norm);
-    ctx->stream = main_stream;
-    KCHK(rc);
+    {
+        StreamScope on_side(ctx, ctx->stream2);
+        KCHK(pc_apply_norm(ctx, b, ctx->d_w, cnt, &fused_norm));
+    }
     HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
     ctx->prep = {KnpSidePrep::LEFT_ENQUEUED, b, fused_norm};
     return KNP_OK;
@@ -221,7 +221,7 @@ int knp_fgmres_prepare(knp_ctx* ctx, const double* b) {
     if (!b) return KNP_E_ARG;
     side_discard(ctx);
     // one GPU only: on distributed contexts ||b|| needs an all-reduce, which the solve does in line
-    if (getenv("KNP_NO_PREPARE") || (ctx->prof_on & ~1) || ctx->halo || ctx->allreduce || ctx->level_comm || ctx->p2p) return KNP_OK;
+    if (getenv("KNP_NO_PREPARE") || class_timing(ctx) || !exchange_free(ctx)) return KNP_OK;
     KCHK(ensure_side_stream(ctx));
     if (!ctx->d_partial_s) {
         HIPCHK(hipMalloc((void**)&ctx->d_partial_s, (size_t)RED_SLOTS * RED_BLOCKS * sizeof(double)));
@@ -263,8 +263,7 @@ static int krylov_begin(knp_ctx* ctx, const double* b, double* x, int32_t max_it
         ctx->err = "restart must be in [1," + std::to_string(GM_MAX_RESTART) + "] and max_it >= 0";
         return KNP_E_ARG;
     }
-    ctx->fields_current = ctx->knod_current = false;   // x is about to change
-    KCHK(drop_ahead(ctx));
+    KCHK(drop_ahead(ctx, ctx->step.x_changing()));   // x is about to change
     KCHK(ensure_work(ctx, restart));
     if (flexible && ctx->pc_kind != KNP_PC_NONE) KCHK(ensure_z(ctx, restart));   // with no preconditioner Z is V: nothing is allocated or copied
     prof_collect_ready(ctx);
@@ -487,12 +486,12 @@ int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doubl
     // finished by then).  The decisions are taken afterwards, the same ones in the same order; an entry that ends or repairs the
     // cycle start discards iteration 0, which has written V_0, V_1, gm, d_t, d_w and reduction slots but not x.  One GPU, no hooks:
     // there every reduction publishes to the pinned mirror and the sequence word, through k_reduce_fin or (KNP_FIN=0) k_proj_norm / k_givens.
-    const bool ahead_ok = ctx->gmres_ahead && ctx->mirror() && ctx->h_seq && ctx->h_seq_dev && !ctx->halo && !ctx->allreduce && !ctx->p2p &&
-                          !ctx->level_comm && ctx->defl_m == 0 && ctx->n_bc == 0 && max_it > 0 && (ctx->prof_on & ~1) == 0;
+    const bool ahead_ok = ctx->gmres_ahead && ctx->mirror() && ctx->h_seq && ctx->h_seq_dev && exchange_free(ctx) && ctx->defl_m == 0 && ctx->n_bc == 0 &&
+                          max_it > 0 && !class_timing(ctx);
     // The update after which the solve returns may also unpack x (k_lincomb_unpack): one GPU, nothing between the update and the
     // caller (krylov_end's halo is a no-op there), every unknown reached from a vertex, a registered target, no class timing.
-    const bool tail_ok = ctx->fused_tail && ctx->tail_ok && ctx->have_tail_target && !ctx->halo && !ctx->allreduce && !ctx->level_comm && !ctx->p2p &&
-                         ctx->defl_m == 0 && ctx->n_bc == 0 && (ctx->prof_on & ~1) == 0;
+    const bool tail_ok = ctx->fused_tail && ctx->tail_ok && ctx->have_tail_target && exchange_free(ctx) && ctx->defl_m == 0 && ctx->n_bc == 0 &&
+                         !class_timing(ctx);
     while (true) {
         // r = M (b - A x)
         KCHK(spmv_A(ctx, x, b, ctx->d_t, true));
@@ -501,13 +500,14 @@ int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doubl
         if (lazy_bnorm && ctx->prep.kind == KnpSidePrep::LEFT_DEFERRED) {   // ||B b||: its cycle goes to the side stream now, behind the launches above
             ctx->prep.kind = KnpSidePrep::LEFT_CONCURRENT;
             HIPCHK(hipStreamWaitEvent(ctx->stream2, ctx->ev_fork, 0));
-            ctx->stream = ctx->stream2;
-            bool fn = false;
-            swap_side_ws(ctx);
-            const int rcs = pc_apply_norm(ctx, b, ctx->d_wb, cnt, &fn, true);
-            swap_side_ws(ctx);
-            ctx->stream = st;
-            KCHK(rcs);
+            {
+                StreamScope on_side(ctx, ctx->stream2);
+                bool fn = false;
+                swap_side_ws(ctx);
+                const int rcs = pc_apply_norm(ctx, b, ctx->d_wb, cnt, &fn, true);
+                swap_side_ws(ctx);   // (back before any return)
+                KCHK(rcs);
+            }
             HIPCHK(hipEventRecord(ctx->ev_join, ctx->stream2));
         }
         bool ahead = ahead_ok && fused_norm;   // true while iteration 0 of this cycle is in flight (or done) and still valid
@@ -572,10 +572,7 @@ int knp_gmres_solve(knp_ctx* ctx, const double* b, double* x, double rtol, doubl
                 KCHK(out_ptrs(ctx, &ctx->tail_target, o, true));
                 hipLaunchKernelGGL(k_lincomb_unpack, dim3(nblocks(ctx->g.n_v)), dim3(NT), 0, st, GL, jd, gm, ctx->g.n_v, ldv, ctx->d_V, x, ctx->d_node_i,
                                    ctx->d_node_e, o, ctx->asm_dmax > 0 ? ctx->d_knod : nullptr);
-                ctx->tail_x = x;
-                ctx->fields_current = true;
-                ctx->knod_current = ctx->asm_dmax > 0;
-                ++ctx->n_fused_tail;
+                ctx->step.tail_done(x, ctx->asm_dmax > 0);
                 KCHK(speculate_asm(ctx));   // the next step's matrix, behind this kernel on the assembly stream
             } else {
                 krylov_update_plain(K, jd, ctx->d_V, x);
