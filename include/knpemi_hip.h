@@ -41,6 +41,9 @@
  *   knp_diag_set_phim_facets / knp_diag_membrane_potential
  *        integral, minimum and maximum of phi_m per membrane tag: what utils/plot_membrane_potentials.py:48-128 reads per cell from
  *        the reference's per-step checkpoints
+ *   knp_activation_arm / knp_activation_step / knp_activation_velocity / knp_diag_set_activation_facets / knp_diag_activation
+ *        activation and repolarisation time, peak and upstroke per membrane vertex, conduction velocity per membrane facet: what
+ *        utils/plot_membrane_potentials*.py would need the reference's checkpoints of every field at every step for
  *   knp_sample_plan_create / knp_sample
  *        scifem.evaluate_function at many points: the slices the reference cuts out of its checkpoints with pyvista
  *        (utils/plot_slices.py, plot_slice_membrane.py, plot_slices_geometries.py)
@@ -509,6 +512,49 @@ int knp_diag_membrane_fluxes(knp_ctx* ctx, const knp_fields* fields, const doubl
 int knp_diag_set_phim_facets(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr /* host [n_tags+1] */,
                              const int32_t* facets /* host [seg_ptr[n_tags]] */);
 int knp_diag_membrane_potential(knp_ctx* ctx, const knp_fields* fields, double* out /* device [n_tags*3] */);
+/* Activation map: per membrane vertex when phi_m first (and last) rose through a threshold, when it fell back, its peak and its
+ * steepest upstroke; per membrane facet the conduction velocity; per tag a summary.  The detector's state belongs to the caller
+ * (device arrays passed by pointer; the library keeps none): v_last [n], state [7][n] (row r of vertex j at state[r*n + j]; rows
+ * t_first, t_last_up, t_repol, v_peak, t_peak, dvdt_max, t_dvdt) and count [n].  vertex [n]: local vertex ids (device int32), e.g. the
+ * unique vertices of the selected tags' owned membrane facets in ascending order; phi_m: the nodal field, device [n_vertices].
+ * knp_activation_arm: v_last = v_peak = phi_m(vertex), t_peak = t, dvdt_max = -inf, t_first = t_last_up = t_repol = t_dvdt = NaN,
+ *   count = 0.
+ * knp_activation_step: one interval [t0, t1] with v0 = v_last, v1 = phi_m(vertex), h = t1 - t0, in this order:
+ *   1. upward crossing iff v0 < thr_up && v1 >= thr_up: tx = t0 + (thr_up - v0)/(v1 - v0) h, count += 1, t_first = tx at the first
+ *      one, t_last_up = tx always;
+ *   2. repolarisation iff count > 0 (after 1), t_repol still NaN and v0 >= thr_down && v1 < thr_down:
+ *      t_repol = t0 + (v0 - thr_down)/(v0 - v1) h (1 needs v1 > v0 and 2 needs v1 < v0: never both in one interval);
+ *   3. peak: v1 > v_peak (strict: the first of equal maxima stays) sets v_peak = v1, t_peak = t1;
+ *   4. steepest upstroke: s = (v1 - v0)/h > dvdt_max sets dvdt_max = s, t_dvdt = t0 + h/2;
+ *   5. v_last = v1.
+ *   All comparisons are plain IEEE: a NaN phi_m records nothing in the interval that ends at it and, being the next v_last, nothing in
+ *   the one after it, and leaves no false crossing.  A listed vertex outside [0, n_vertices) reads as NaN.
+ * Both run one kernel on the context's stream, one lane per listed vertex, with no host copy and no synchronisation.  KNP_E_ARG (with
+ * knp_last_error text, the buffers untouched) for a null pointer, n < 0, t1 <= t0 or a non-finite threshold; n == 0 is a successful no-op.
+ * knp_activation_velocity: T is a nodal activation time, device [n_vertices], NaN where a vertex did not fire or is not listed;
+ *   facets [n_facets]: indices into the Gamma list of knp_create (device int32).  Per listed facet out[(1+dim) i] = speed [m/s] and
+ *   out[(1+dim) i + 1 ...] = the unit direction of propagation [dim], from the surface gradient g of T's P1 interpolant: speed = 1/|g|,
+ *   direction = g/|g|.  2D (segments): e = x1 - x0, L = |e|, d = T1 - T0, speed = L/|d|, direction = sign(d) e/L.  3D (triangles):
+ *   e1 = x1 - x0, e2 = x2 - x0, a = e1.e1, b = e1.e2, c = e2.e2, det = a c - b^2, d1 = T1 - T0, d2 = T2 - T0,
+ *   g = [(c d1 - b d2) e1 + (a d2 - b d1) e2]/det, |g|^2 = (c d1^2 - 2 b d1 d2 + a d2^2)/det.  A facet is valid iff all its T are
+ *   finite, its measure is not zero and |g| > 0 (2D: d != 0); an invalid facet, and a listed index outside the Gamma list, writes NaN in all 1 + dim slots.
+ *   KNP_E_ARG for a null pointer or n_facets < 0; n_facets == 0 is a successful no-op.
+ * knp_diag_set_activation_facets: a tag map of membrane facets like knp_diag_set_phim_facets (same validation, same combine rule),
+ *   kept apart from the other maps.  Synchronous.
+ * knp_diag_activation: out[5t ..] = over the facets F of tag t (sum |F| [F valid], sum |F| speed(F) [F valid], min and max of T over
+ *   the vertices of the facets (fmin / fmax: NaN dropped), sum |F|/d * number of F's vertices with a finite T).  A tag without facets
+ *   gives (0, 0, +inf, -inf, 0).  No atomics, partials combined in a fixed order: the same bits on every run.  KNP_E_STATE before a map
+ *   is set, KNP_E_ARG for a null argument; n_tags == 0 is a successful no-op. */
+int knp_activation_arm(knp_ctx* ctx, int32_t n, const int32_t* vertex /* device [n] */, const double* phi_m /* device [n_vertices] */,
+                       double t, double* v_last /* device [n] */, double* state /* device [7*n] */, int32_t* count /* device [n] */);
+int knp_activation_step(knp_ctx* ctx, int32_t n, const int32_t* vertex /* device [n] */, const double* phi_m /* device [n_vertices] */,
+                        double t0, double t1, double thr_up, double thr_down, double* v_last /* device [n] */,
+                        double* state /* device [7*n] */, int32_t* count /* device [n] */);
+int knp_activation_velocity(knp_ctx* ctx, int32_t n_facets, const int32_t* facets /* device [n_facets] */,
+                            const double* T /* device [n_vertices] */, double* out /* device [n_facets*(1+dim)] */);
+int knp_diag_set_activation_facets(knp_ctx* ctx, int32_t n_tags, const int32_t* seg_ptr /* host [n_tags+1] */,
+                                   const int32_t* facets /* host [seg_ptr[n_tags]] */);
+int knp_diag_activation(knp_ctx* ctx, const double* T /* device [n_vertices] */, double* out /* device [n_tags*5] */);
 /* Field sampling: P1 evaluation of nodal fields at arbitrary points (grids, slices), located on the device once per point set.
  * Rule: cell T contains p iff all dim+1 barycentric weights of p in T are >= -1e-9; among the containing cells the lowest local cell
  *   index wins; the stored weights are clipped to [0, 1] and renormalised to sum 1.  Only owned cells are searched, and with side 0 / 1

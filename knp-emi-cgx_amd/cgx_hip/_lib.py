@@ -138,6 +138,11 @@ SIGNATURES = {
     "knp_diag_membrane_fluxes": (C.c_int, [vp, C.POINTER(Fields), vp, vp, f64p, f64p, vp]),
     "knp_diag_set_phim_facets": (C.c_int, [vp, C.c_int32, i32p, i32p]),
     "knp_diag_membrane_potential": (C.c_int, [vp, C.POINTER(Fields), vp]),
+    "knp_activation_arm": (C.c_int, [vp, C.c_int32, vp, vp, C.c_double, vp, vp, vp]),
+    "knp_activation_step": (C.c_int, [vp, C.c_int32, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp, vp]),
+    "knp_activation_velocity": (C.c_int, [vp, C.c_int32, vp, vp, vp]),
+    "knp_diag_set_activation_facets": (C.c_int, [vp, C.c_int32, i32p, i32p]),
+    "knp_diag_activation": (C.c_int, [vp, vp, vp]),
     "knp_sample_plan_create": (C.c_int, [vp, C.c_int32, f64p, C.c_int32, C.c_int32, i32p, i32p, f64p, f64p, i32p, i32p]),
     "knp_sample_plan_get": (C.c_int, [vp, C.c_int32, i32p, f64p]),
     "knp_sample": (C.c_int, [vp, C.c_int32, C.c_int32, C.POINTER(vp), C.POINTER(vp), C.c_double, vp]),

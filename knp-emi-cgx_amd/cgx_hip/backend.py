@@ -29,6 +29,11 @@ def _i32(a):
     return a.ctypes.data_as(_lib.i32p)
 
 
+def _tp(t):
+    """a device tensor as a pointer argument"""
+    return C.c_void_p(t.data_ptr())
+
+
 def deflation_node_modes(node_i, node_e, n_vertices_owned, n_nodes_owned, vertex_mode_i, ecs_mode, bc_dofs=None):
     """``node_mode`` of knp_set_deflation: the mode of every owned node (intracellular: that of its component or -1, extracellular:
     ``ecs_mode``), and -1 where the node's potential row is a Dirichlet row -- the correction is added after the Dirichlet copy, so a
@@ -81,7 +86,54 @@ class StateUpdate:
                          int(p.state_rush_larsen), int(p.state_substeps))
 
 
-class Backend(StateUpdate):
+class ActivationCalls:
+    """The activation-map entry points on a backend (csrc/knp_activation.inc; cgx_hip/activation.py is their caller).  The detector's
+    state belongs to the caller; the summary's facet map lives in the context, one per backend, so the record of which groups it
+    holds is kept here: any number of ``ActivationMap``s share it and each call sets the groups it needs."""
+
+    _activation = None      # the diagnostics.FacetGroupLayout of the map now set in the context
+
+    def activation_arm(self, vertex, phi, t, v_last, state, count):
+        """reset the detector's state at time ``t`` (device tensors; enqueued)"""
+        if vertex.numel():
+            self.check(self.lib.knp_activation_arm(self.ctx, vertex.numel(), _tp(vertex), _tp(phi), float(t), _tp(v_last), _tp(state), _tp(count)))
+
+    def activation_step(self, vertex, phi, t0, t1, thr_up, thr_down, v_last, state, count):
+        """one detector launch over the interval [t0, t1] (enqueued)"""
+        if vertex.numel():
+            self.check(self.lib.knp_activation_step(self.ctx, vertex.numel(), _tp(vertex), _tp(phi), float(t0), float(t1), float(thr_up),
+                                                    float(thr_down), _tp(v_last), _tp(state), _tp(count)))
+
+    def activation_velocity(self, facets, T):
+        """speed and unit direction per listed facet from the nodal time ``T``: a new device tensor [n_facets, 1 + dim] (enqueued)"""
+        dim = self.p.local_mesh.coords.shape[1]
+        out = torch.empty((facets.numel(), 1 + dim), dtype=torch.float64, device=self.device)
+        if facets.numel():
+            self.check(self.lib.knp_activation_velocity(self.ctx, facets.numel(), _tp(facets), _tp(T), _tp(out)))
+        return out
+
+    def set_activation_groups(self, groups):
+        """The facet groups of ``activation_summary`` (``diagnostics.FacetGroupLayout``, knp_diag_set_activation_facets); a call with
+        the groups already set does nothing.  Returns the layout."""
+        from .diagnostics import FacetGroupLayout
+        groups = tuple(tuple(int(t) for t in g) for g in groups)
+        if self._activation is None or self._activation.groups != groups:
+            lay = FacetGroupLayout(self.p, groups)
+            self._activation = None
+            self.check(self.lib.knp_diag_set_activation_facets(self.ctx, lay.n_groups, _i32(lay.seg_ptr), _i32(lay.facets) if lay.facets.size else None))
+            self._activation = lay
+        return self._activation
+
+    def activation_summary(self, groups, T):
+        """(valid area, area x speed, first time, last time, activated area) per group of ``groups`` from the nodal time ``T``: a new
+        device tensor [n_groups, 5], sized by the map that is set, and that map's layout (enqueued)"""
+        lay = self.set_activation_groups(groups)
+        out = torch.empty((lay.n_groups, 5), dtype=torch.float64, device=self.device)
+        self.check(self.lib.knp_diag_activation(self.ctx, _tp(T), _tp(out)))
+        return out, lay
+
+
+class Backend(StateUpdate, ActivationCalls):
     def __init__(self, problem):
         self.p = problem
         self.lib = _lib.load()

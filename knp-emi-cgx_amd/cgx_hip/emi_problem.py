@@ -22,7 +22,7 @@ import torch
 import yaml
 
 from . import _lib, fem
-from .backend import StateUpdate
+from .backend import ActivationCalls, StateUpdate
 from . import mesh as meshmod
 from .emi_models import HH_model, IonicModel, Passive_model, g_syn_none
 from .fem import Function, FunctionSpace
@@ -41,7 +41,7 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-class EmiBackend(StateUpdate):
+class EmiBackend(StateUpdate, ActivationCalls):
     """Owns the ``knp_ctx`` of an EMI problem and the device vectors b, x [n_nodes]."""
 
     def __init__(self, problem, gamma_prog):
@@ -423,6 +423,12 @@ class ProblemEMI(MixedDimensionalProblem):
         expressions and ``tags`` of ``assemble_scalar_membrane``)"""
         from .fields import FacetField
         return FacetField(self, expr, tags, degree, name)
+
+    def activation_map(self, threshold, repolarisation_threshold=None, tags=None):
+        """an ``activation.ActivationMap`` of ``phi_M`` on the membranes tagged ``tags`` (default every tag of ``gamma_tags``), armed
+        now: call its ``update()`` after every step, then ``result()``, ``velocity()``, ``per_tag()``"""
+        from .activation import ActivationMap
+        return ActivationMap(self, threshold, repolarisation_threshold, tags)
 
     def setup_preconditioner(self):
         """The preconditioner matrix is the EMI matrix itself (with the Dirichlet elimination).  The reference's P = sigma K + M per side

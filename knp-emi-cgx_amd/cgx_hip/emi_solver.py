@@ -60,6 +60,10 @@ class SolverEMI:
     amg_cheby_degree = 1
     amg_fp32 = False
     amg_setup = "host"     # "host" (SciPy, cgx_hip/amg.py) | "gpu" (torch sparse products, cgx_hip/amg_gpu.py)
+    # True, or a mapping with threshold [V], repolarisation_threshold [V], tags (the output key save_activation of the KNP-EMI solver):
+    # activation times, peaks and conduction velocity on the membrane, armed before the first step, one detector launch per step,
+    # activation*.npy in the output directory after the last (cgx_hip/activation.py).  Off: nothing is allocated or launched.
+    save_activation = False
 
     def __init__(self, problem: ProblemEMI, use_direct_solver: bool = True, save_xdmfs: bool = False, save_pngs: bool = False,
                  save_mat: bool = False):
@@ -152,6 +156,9 @@ class SolverEMI:
         rtol = self.direct_rtol if self.direct_solver else self.ksp_rtol
         norm = "unpreconditioned" if self.direct_solver else self.norm_type
         dt = float(p.dt.value)
+        from .activation import ActivationMap, parse_activation_key
+        act = parse_activation_key({"save_activation": self.save_activation}, p.gamma_tags)
+        self.activation = ActivationMap(p, **act) if act is not None else None
         be.timer_mark()
         try:
             for i in range(self.time_steps):
@@ -180,6 +187,8 @@ class SolverEMI:
                     self.save_xdmf()
                 if self.save_pngs:
                     self.save_png()
+                if self.activation is not None:
+                    self.activation.update()
         finally:
             t = be.timer_read()
             self.assembly_time = list(t[0::2][:len(self.iterations)])
@@ -190,6 +199,8 @@ class SolverEMI:
         self.tot_assembly_time, self.tot_solver_time = float(sum(self.assembly_time)), float(sum(self.solve_time))
         if self.save_pngs:
             self.print_figures()
+        if self.activation is not None:
+            self.activation.save(self.out_file_prefix)
         if self.save_mat:
             import scipy.sparse as sp
             sp.save_npz(os.path.join(self.out_file_prefix, "Amat.npz"), be.csr())

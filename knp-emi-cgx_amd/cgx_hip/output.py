@@ -306,6 +306,13 @@ class RunOutput:
             self.probe_idx = torch.as_tensor(self.probes["vertex"][self.probe_cols], dtype=torch.int64, device=be.device)
             self.probe_fields = [p.phi_m_prev] + ([p.n, p.m, p.h] if hasattr(p, "n") else [])
             self.probe_rows = torch.zeros((len(self.probe_fields), n_rec, len(self.probe_cols)), dtype=torch.float64, device=be.device)
+        # activation map (output key save_activation): armed here, on the state that record 0 sees, then one detector launch per
+        # record; read once in save_activation()
+        self.activation = None
+        if getattr(solver, "save_activation", None) is not None:
+            from .activation import ActivationMap
+            os.makedirs(self.prefix, exist_ok=True)
+            self.activation = ActivationMap(p, **solver.save_activation)
         # fields on grids and slices (output key sample_grids): per entry one located GridSampler and one preallocated device tensor
         # [records, fields, *shape]; a record is one gather launch, the tensors are read once in save_sample_grids()
         self.grids = []
@@ -377,6 +384,8 @@ class RunOutput:
             if len(self.probe_cols):
                 for k, fn in enumerate(self.probe_fields):
                     torch.index_select(fn.x.array, 0, self.probe_idx, out=self.probe_rows[k, r])
+        if self.activation is not None and i > 0:
+            self.activation.update()
         if self.grids and (i % s.sample_interval == 0):
             for g in self.grids:
                 g["sampler"](g["f_i"], g["f_e"], out=g["buf"][i // s.sample_interval])
@@ -600,6 +609,10 @@ class RunOutput:
         np.save(out + "phi_m_points_xyz.npy", self.probes["xyz"])
         if len(self.probe_fields) == 4:
             np.save(out + "gating_points.npy", np.ascontiguousarray(np.transpose(pts[1:], (1, 2, 0))))
+
+    def save_activation(self):
+        """the six activation*.npy files of ``ActivationMap.save``"""
+        self.activation.save(self.p.output_dir)
 
     def save_sample_grids(self):
         """Per ``sample_grids`` entry: grid_<name>.npy [records, fields, *shape] (the merged fields: the _i function inside intracellular

@@ -919,6 +919,12 @@ class ProblemKNPEMI(MixedDimensionalProblem):
         from .fields import FacetField
         return FacetField(self, expr, tags, degree, name)
 
+    def activation_map(self, threshold, repolarisation_threshold=None, tags=None):
+        """an ``activation.ActivationMap`` of ``phi_m_prev`` on the membranes tagged ``tags`` (default every tag of ``gamma_tags``),
+        armed now: call its ``update()`` after every step, then ``result()``, ``velocity()``, ``per_tag()``"""
+        from .activation import ActivationMap
+        return ActivationMap(self, threshold, repolarisation_threshold, tags)
+
     def print_conservation(self):
         """Total ion amounts and, per intracellular tag, volume, membrane area and charge: the reference's lines
         (KNPEMIx_problem.py:807-843), printed on rank 0 from ``ion_budget()``."""

@@ -80,6 +80,11 @@ class SolverKNPEMI:
     # vertex per tag every membrane_potential_interval steps (phi_m_tags.npy, phi_m_points.npy); None: off
     membrane_potential_tags = None
     membrane_potential_interval = 1
+    # output key save_activation (True, or a mapping with threshold [V], repolarisation_threshold [V], tags): activation and
+    # repolarisation time, peak and upstroke per membrane vertex, conduction velocity per membrane facet (activation*.npy); the default
+    # threshold is 0 V because the solver does not know a membrane model's resting value (-0.02 V is common).  Holds the
+    # parsed keyword arguments of the ActivationMap, None: off; the map itself is ``output.activation``
+    save_activation = None
     # output keys sample_grids (a list of named point lattices) / sample_interval (default: save_interval): the merged fields on each
     # lattice every sample_interval steps (grid_<name>.npy and its _tags, _xyz, _t files); empty: off
     sample_grids = ()
@@ -122,6 +127,8 @@ class SolverKNPEMI:
         self.save_fluxes = bool(out.get("save_fluxes", False))
         from .output import parse_membrane_potential_keys
         self.membrane_potential_tags, self.membrane_potential_interval = parse_membrane_potential_keys(out, problem.gamma_tags)
+        from .activation import parse_activation_key
+        self.save_activation = parse_activation_key(out, problem.gamma_tags)
         if "save_interval" in out:
             self.save_interval = out["save_interval"]
         from .output import parse_sample_grids
@@ -407,7 +414,8 @@ class SolverKNPEMI:
         from .output import RunOutput
         self.output = RunOutput(self) if (self.save_pngs or self.save_dat or self.save_cpoints or self.save_xdmfs or p.point_evaluation
                                           or self.save_ion_budget or self.save_fluxes
-                                          or self.membrane_potential_tags is not None or self.sample_grids or self.functionals
+                                          or self.membrane_potential_tags is not None or self.save_activation is not None
+                                          or self.sample_grids or self.functionals
                                           or self.fields) else None
         if self.output is not None:
             self.output.record(0)
@@ -569,6 +577,8 @@ class SolverKNPEMI:
             self.output.save_fluxes()
         if self.membrane_potential_tags is not None and self.output is not None:
             self.output.save_membrane_potentials()
+        if self.save_activation is not None and self.output is not None:
+            self.output.save_activation()
         if self.sample_grids and self.output is not None:
             self.output.save_sample_grids()
         if self.functionals and self.output is not None:

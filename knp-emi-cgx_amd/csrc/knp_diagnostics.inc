@@ -35,6 +35,15 @@ struct DiagPhim {         // (integral, minimum, maximum) of phi_m
     // fmin / fmax drop a NaN: a NaN phi_m shows in the integral, not in the minimum and maximum (stated in the ABI comment)
     __device__ static DiagPhim op(const DiagPhim& a, const DiagPhim& b) { return {{a.v[0] + b.v[0], fmin(a.v[1], b.v[1]), fmax(a.v[2], b.v[2])}}; }
 };
+struct DiagActivation {   // (valid area, area x speed, first and last activation time, activated area) of k_diag_activation (knp_activation.inc)
+    static constexpr int N = 5;
+    double v[5];
+    __device__ static DiagActivation identity() { return {{0.0, 0.0, HUGE_VAL, -HUGE_VAL, 0.0}}; }
+    // fmin / fmax drop a NaN: a vertex that never fired does not enter the first and last times
+    __device__ static DiagActivation op(const DiagActivation& a, const DiagActivation& b) {
+        return {{a.v[0] + b.v[0], a.v[1] + b.v[1], fmin(a.v[2], b.v[2]), fmax(a.v[3], b.v[3]), a.v[4] + b.v[4]}};
+    }
+};
 
 // One partial per run of equal keys inside the block's chunk (keys ascending over the live threads, which form a prefix).
 template <class V, int BT>
@@ -324,6 +333,7 @@ void knp_diag_free(knp_ctx* ctx) {
     diag_map_free(ctx->diag_flux);
     dev_free(ctx->d_flux_rec);
     diag_map_free(ctx->diag_phim);
+    diag_map_free(ctx->diag_act);
     dev_free(ctx->diag_code);
     ctx->diag_n_instr = ctx->diag_n_regs = ctx->diag_n_consts = 0;
     ctx->diag_prog = false;

@@ -484,6 +484,8 @@ struct knp_ctx {
     double2* d_flux_rec = nullptr;   // [diag_flux.n * (dim == 3 ? 8 : 7)] 16-byte units, layout at k_diag_fluxes
     // membrane potential per tag (knp_diag_set_phim_facets): a tag map of its own
     KnpDiagMap diag_phim;
+    // activation summary per tag (knp_diag_set_activation_facets, knp_activation.inc): a tag map of its own
+    KnpDiagMap diag_act;
     int32_t* diag_code = nullptr;
     int diag_n_instr = 0, diag_n_regs = 0, diag_n_consts = 0;
     double diag_consts[KNP_DIAG_MAX_CONSTS] = {};   // host copy: passed to the kernel by value at every launch

@@ -4936,6 +4936,8 @@ int knp_amg_get_level_info(const knp_ctx* ctx, int32_t hier, int32_t level, int3
 
 // per-tag diagnostics: ion amounts per cell tag, membrane integrals of one program (knp_diag_*)
 #include "knp_diagnostics.inc"
+// activation map: event detector per membrane vertex, conduction velocity per membrane facet, their per-tag summary (knp_activation_*)
+#include "knp_activation.inc"
 
 // field sampling at arbitrary points: point locator, interpolation weights, one gather per record (knp_sample_*)
 #include "knp_sample.inc"
