@@ -843,6 +843,85 @@ int knp_refine_facets(int32_t dim, int64_t n_facets, int64_t n_vertices, int64_t
 int knp_refine_prolong(int32_t n_fields, int64_t n_vertices, int64_t n_edges, const int32_t* edge_vertices, const double* in, int64_t ld_in,
                        double* out, int64_t ld_out, void* stream);
 
+/* ---- level-set surfaces (csrc/knp_surface.inc; cgx_hip/surfaces.py) -----------------------------------------------------------
+ * The cut of a set of simplices by the level s = iso of a nodal function: the clipped boundary of a set of cells, the slice / iso-
+ * surface through them, contour lines on membrane facets.  Context-free like the refinement: every pointer is DEVICE memory (the
+ * origin / normal of knp_surface_plane and the pointer tables of knp_surface_gather apart: host), every launch goes to `stream`,
+ * nothing is read back and nothing is synchronised.  KNP_E_ARG, with nothing launched, for a null pointer, a bad nodes_per_item /
+ * dim or a count outside [0, 2^31 - 1] (n_vertices >= 1); KNP_E_HIP when a launch fails.  A zero count is a successful no-op.
+ *
+ * Definitions.
+ *   An ITEM is a simplex of npi = 3 or 4 local vertex ids with a side byte (0 intracellular, 1 extracellular) and a reference id (its
+ *   tag): a triangle is a cell of a 2D mesh (dim 2) or a membrane facet of a 3D mesh (dim 3), a tetrahedron a cell of a 3D mesh.
+ *   A BOUNDARY FACET has npi - 1 vertex ids, stored in an order whose normal points out of its item (3D: (v1 - v0) x (v2 - v0); 2D:
+ *   the item lies to the left of v0 -> v1), and the index of that item, whose side and tag it takes.
+ *   t_v = s_v - iso, one fp64 subtraction.  Vertex v is INSIDE iff t_v >= 0: a vertex exactly on the level is inside.  An item or
+ *   boundary facet with a NaN t or a vertex id outside [0, nv) emits nothing; so does a boundary facet whose item index is out of range.
+ *   An OUTPUT VERTEX has the key (side, a, b): a == b and w = 0 for an original vertex; for the cut point of the edge a-b, a is the
+ *   inside and b the outside vertex and w = t_a / (t_a - t_b) (t_a >= 0 > t_b: no cancellation).  As a 64-bit integer the key is
+ *   side * 2^62 + a * nv + b; the unique keys in ascending order number the output vertices.  The position and every field is
+ *   (1 - w) F[a] + w F[b], every operation rounded on its own, F the side's array: an original vertex returns F[a] exactly.
+ *   CUT FACES of a tetrahedron, p < q < u the inside local indices, r < t < u' the outside ones, xy the cut point of the edge x-y:
+ *       1 inside / 3 outside   triangle (pr, pt, pu')          sequence (p, r, t, u')   reversed iff sign < 0
+ *       3 inside / 1 outside   triangle (pr, qr, ur)           sequence (r, p, q, u)    reversed iff sign > 0
+ *       2 inside / 2 outside   quad (pr, pt, qt, qr), split    sequence (p, q, r, t)    reversed iff sign < 0
+ *                              as (0, 1, 2), (0, 2, 3)
+ *   sign = sign(D) * parity(sequence), D = det[x1 - x0, x2 - x0, x3 - x0] of the item in its stored order (every operation rounded on
+ *   its own, first row expanded: (e00 c0 + e01 c1) + e02 c2), parity the sign of the sequence as a permutation of the local indices:
+ *   the sign of det[r-p, t-p, u'-p], det[p-r, q-r, u-r], det[q-p, r-p, t-p].  A reversed triangle swaps its last two vertices.  The
+ *   normal of a cut face then points from the inside vertices to the outside ones, out of the kept solid; the decision never looks at
+ *   the emitted triangle, so degenerate output is oriented like its neighbours.
+ *   A triangle item gives a SEGMENT by the same rule one dimension down: 1 inside (p; r < t) -> (pr, pt), sequence (p, r, t), reversed
+ *   iff sign < 0; 2 inside (p < q; r) -> (pr, qr), sequence (r, p, q), reversed iff sign > 0; a reversed segment swaps its ends.  In
+ *   2D D = det[x1 - x0, x2 - x0]; for a facet of a 3D mesh D = +1: the stored order is the orientation.  Direction convention: seen
+ *   from the side the item's normal (x1 - x0) x (x2 - x0) points to (2D: from +z) the kept part lies to the LEFT of the segment.
+ *   A boundary facet is CLIPPED to the inside, keeping its cyclic order: 3 inside the facet itself; 1 inside (a; b, c next in cyclic
+ *   order) (a, ab, ac); 2 inside (a, b before the outside c in cyclic order) (a, b, bc) and (a, bc, ac); 0 nothing.  An edge (2D):
+ *   both inside itself, v0 only (v0, v0v1), v1 only (v1v0, v1).
+ *   ORDER: the cut elements of item 0, 1, .. (local order as above), then the clipped elements of boundary facet 0, 1, ..: the scan
+ *   of the counts fixes it, the same input gives the same arrays bit for bit.  Zero-area elements (a vertex exactly on the level)
+ *   are kept.  Every element carries its item, that item's reference id and a kind (0 cut, 1 boundary).
+ *
+ * Sequence of a build: [knp_surface_plane] -> knp_surface_count -> the caller's exclusive scan of counts (int64 offsets) and one
+ * read-back of the total -> knp_surface_emit -> the caller's sort + deduplication of element_keys -> knp_surface_vertices,
+ * knp_surface_remap.  Per record: knp_surface_gather.  Kernels launch at most 1024 blocks of 256 lanes and stride over longer lists. */
+#define KNP_SURFACE_MAX_FIELDS 16
+/* s[v] = ((x0 - o0) n0 + (x1 - o1) n1) + (x2 - o2) n2, every operation rounded on its own; origin, normal: HOST [dim] */
+int knp_surface_plane(int32_t dim, int64_t n_vertices, const double* coords, const double* origin, const double* normal, double* s,
+                      void* stream);
+/* counts [n_items + n_bfacets]: elements each item, then each boundary facet, emits */
+int knp_surface_count(int32_t nodes_per_item, int64_t n_items, int64_t n_vertices, const int32_t* items, int64_t n_bfacets,
+                      const int32_t* bfacets, const int32_t* bfacet_item, const double* s, double iso, int32_t* counts, void* stream);
+/* offsets [n_items + n_bfacets]: the exclusive scan of counts; element_keys [n_elements * (npi - 1)], element_item / element_tag /
+ * element_kind [n_elements].  (dim, npi) is (2, 3), (3, 3) or (3, 4); coords may be NULL for (3, 3).  An item whose elements would
+ * not fit into n_elements writes nothing. */
+int knp_surface_emit(int32_t dim, int32_t nodes_per_item, int64_t n_items, int64_t n_vertices, const int32_t* items, const uint8_t* item_side,
+                     const int32_t* item_ref, int64_t n_bfacets, const int32_t* bfacets, const int32_t* bfacet_item, const double* s, double iso,
+                     const double* coords, const int64_t* offsets, int64_t n_elements, int64_t* element_keys, int32_t* element_item,
+                     int32_t* element_tag, uint8_t* element_kind, void* stream);
+/* unique_keys [n_out] sorted -> vertex_a, vertex_b, vertex_w, vertex_side [n_out] and xyz [n_out * dim] */
+int knp_surface_vertices(int32_t dim, int64_t n_vertices, int64_t n_out, const int64_t* unique_keys, const double* s, double iso,
+                         const double* coords, int32_t* vertex_a, int32_t* vertex_b, double* vertex_w, uint8_t* vertex_side, double* xyz,
+                         void* stream);
+/* elements [n_keys] = position of element_keys[i] among unique_keys (binary search) */
+int knp_surface_remap(int64_t n_keys, int64_t n_out, const int64_t* element_keys, const int64_t* unique_keys, int32_t* elements, void* stream);
+/* out[f * n_out + k] = (1 - w_k) F_f[a_k] + w_k F_f[b_k], F_f = fields_i[f] where vertex_side[k] == 0, fields_e[f] where it is 1; NaN where
+ * that pointer is NULL.  fields_i / fields_e: HOST tables of n_fields device pointers [n_vertices each]; one of the tables may be NULL.
+ * n_fields in 0 .. KNP_SURFACE_MAX_FIELDS.  One launch (n_fields in the grid's y), no host copy, no synchronisation. */
+int knp_surface_gather(int32_t n_fields, int64_t n_out, const int32_t* vertex_a, const int32_t* vertex_b, const double* vertex_w,
+                       const uint8_t* vertex_side, const double* const* fields_i, const double* const* fields_e, double* out, void* stream);
+/* measure [n_elements]: length of a segment (nodes_per_element 2) or area of a triangle (3, dim 3) from xyz [n_out * dim]; NaN for an
+ * element with a vertex number outside [0, n_out) */
+int knp_surface_measure(int32_t dim, int32_t nodes_per_element, int64_t n_elements, int64_t n_out, const int32_t* elements, const double* xyz,
+                        double* measure, void* stream);
+/* the launch geometry of the last knp_surface_* call of this process that launched a kernel (host state only; not thread-safe): the
+ * first min(n, KNP_SI_COUNT) slots are written.  KNP_E_ARG for a null argument or n <= 0. */
+enum { KNP_SK_PLANE = 1, KNP_SK_COUNT = 2, KNP_SK_EMIT = 3, KNP_SK_VERTICES = 4, KNP_SK_REMAP = 5, KNP_SK_GATHER = 6, KNP_SK_MEASURE = 7 };
+enum { KNP_SI_KERNEL = 0 /* KNP_SK_* of the call, 0: none yet */, KNP_SI_BLOCKS = 1 /* grid x */, KNP_SI_THREADS = 2 /* lanes per block */,
+       KNP_SI_N = 3 /* work items */, KNP_SI_TRIPS = 4 /* iterations of the grid-stride loop: > 1 when the list wrapped */,
+       KNP_SI_GRID_Y = 5 /* grid y (fields of a gather) */, KNP_SI_COUNT = 6 };
+int knp_surface_get_info(int32_t* out /* host [n] */, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,7 +188,20 @@ SIGNATURES = {
     "knp_refine_cells": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp]),
     "knp_refine_facets": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp, vp]),
     "knp_refine_prolong": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, vp, vp, C.c_int64, vp, C.c_int64, vp]),
+    # context-free: device pointers and a stream (cgx_hip/surfaces.py); origin / normal and the pointer tables of the gather are host
+    "knp_surface_plane": (C.c_int, [C.c_int32, C.c_int64, vp, f64p, f64p, vp, vp]),
+    "knp_surface_count": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, vp, C.c_int64, vp, vp, vp, C.c_double, vp, vp]),
+    "knp_surface_emit": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, vp, vp, vp, C.c_int64, vp, vp, vp, C.c_double, vp, vp, C.c_int64,
+                                   vp, vp, vp, vp, vp]),
+    "knp_surface_vertices": (C.c_int, [C.c_int32, C.c_int64, C.c_int64, vp, vp, C.c_double, vp, vp, vp, vp, vp, vp, vp]),
+    "knp_surface_remap": (C.c_int, [C.c_int64, C.c_int64, vp, vp, vp, vp]),
+    "knp_surface_gather": (C.c_int, [C.c_int32, C.c_int64, vp, vp, vp, vp, C.POINTER(vp), C.POINTER(vp), vp, vp]),
+    "knp_surface_measure": (C.c_int, [C.c_int32, C.c_int32, C.c_int64, C.c_int64, vp, vp, vp, vp]),
+    "knp_surface_get_info": (C.c_int, [i32p, C.c_int]),
 }
+KNP_SURFACE_MAX_FIELDS = 16
+SURFACE_INFO = ("kernel", "blocks", "threads", "n", "trips", "grid_y")      # KNP_SI_* in order
+SURFACE_KERNELS = {"plane": 1, "count": 2, "emit": 3, "vertices": 4, "remap": 5, "gather": 6, "measure": 7}      # KNP_SK_*
 
 _lib = None
 

@@ -181,6 +181,29 @@ class ActivationMap:
                 a.index_copy_(0, self._vertex64, self.state[row])
         return self._functions
 
+    def isochrones(self, levels):
+        """Contour lines of the activation time on the map's membrane facets, exact on the mesh (cgx_hip/surfaces.py): per level a
+        dict with ``level``, ``xyz`` [n, 3] in metres, ``segments`` [m, 2] (indices into ``xyz``), ``facet`` [m] (index into
+        ``facets``), ``tag`` [m] and ``length`` [m].  Seen from the side a facet's stored normal points to, the part that fired at or
+        after the level lies to the left of a segment.  A facet with a vertex that did not fire (NaN) is skipped.  3D only: the
+        contour of a 2D mesh's membrane (a set of edges) would be points, and a 2D membrane raises ``ValueError``.  One build -- one
+        read-back of a count -- and one copy of the result per level."""
+        from .surfaces import LevelSetSurface
+        if self.dim != 3:
+            raise ValueError("isochrones are lines on the membrane surface of a 3D mesh; on a 2D mesh the membrane is a set of edges")
+        levels = [float(v) for v in np.atleast_1d(levels)]
+        if not all(np.isfinite(levels)):
+            raise ValueError("isochrone levels must be finite")
+        if getattr(self, "_isolines", None) is None:
+            self._isolines = LevelSetSurface(self.problem, self.facet_vertices, np.zeros(len(self.facets), dtype=np.uint8), self.facet_tag)
+        S, T, out = self._isolines, self.activation_time(), []
+        for lv in levels:
+            S.build(T, lv)
+            item = S.element_item.cpu().numpy().astype(np.int64)
+            out.append({"level": lv, "xyz": S.xyz.cpu().numpy(), "segments": S.elements.cpu().numpy().astype(np.int64), "facet": item,
+                        "tag": S.element_tag.cpu().numpy().astype(np.int64), "length": S.measure().cpu().numpy()})
+        return out
+
     # ---- files
     def save(self, out_dir):
         """activation.npy [n, 9] (``RESULT_COLUMNS``), activation_vertices.npy [n] local vertex ids, activation_xyz.npy [n, dim] in m,

@@ -88,6 +88,7 @@ class SolverEMI:
         self.backend = problem.backend
         self.iterations, self.reasons, self.solve_time, self.assembly_time = [], [], [], []
         self.out = None
+        self.surfaces = []         # add_surface(): (name, LevelSetSurface, fields, interval)
         if save_xdmfs or save_pngs or save_mat:
             os.makedirs(self.out_file_prefix, exist_ok=True)
         if save_xdmfs:
@@ -146,6 +147,16 @@ class SolverEMI:
             self.print("Setting up iterative solver ...")
         self._solver_ready = True
 
+    def add_surface(self, name, S, fields=None, interval=None):
+        """Record nodal fields on the built surface ``S`` (cgx_hip/surfaces.py; ``problem.clip_surface(...)``) at step 0 and at every
+        ``interval``-th step (default ``save_interval``), one gather launch per record: ``fields`` None for ``phi`` (phi_i on
+        intracellular elements, phi_e on extracellular ones) or a mapping name -> (function_i, function_e).  The run ends with
+        surface_<name>.xdmf / .h5 in the output directory.  Call it before ``solve()``."""
+        from .surfaces import check_add_surface
+        if self._solver_ready:
+            raise RuntimeError("add_surface() must be called before solve()")
+        self.surfaces.append(check_add_surface(self, name, S, fields, interval, self.surfaces))
+
     # ---- time loop
     def solve(self):
         p = self.problem
@@ -159,6 +170,13 @@ class SolverEMI:
         from .activation import ActivationMap, parse_activation_key
         act = parse_activation_key({"save_activation": self.save_activation}, p.gamma_tags)
         self.activation = ActivationMap(p, **act) if act is not None else None
+        recorders = []
+        if self.surfaces:
+            from .surfaces import SurfaceRecorder, named_functions
+            recorders = [SurfaceRecorder(name, S, *named_functions(p, fields), interval, self.time_steps, self.out_file_prefix)
+                         for name, S, fields, interval in self.surfaces]
+            for r in recorders:
+                r.record(0, float(p.t.value))
         be.timer_mark()
         try:
             for i in range(self.time_steps):
@@ -189,7 +207,11 @@ class SolverEMI:
                     self.save_png()
                 if self.activation is not None:
                     self.activation.update()
+                for r in recorders:
+                    r.record(i + 1, float(p.t.value))
         finally:
+            for r in recorders:
+                r.save()
             t = be.timer_read()
             self.assembly_time = list(t[0::2][:len(self.iterations)])
             self.solve_time = list(t[1::2][:len(self.iterations)])

@@ -323,6 +323,17 @@ class RunOutput:
             _, f_i, f_e = merged_functions(p, g["fields"])
             buf = torch.zeros((g["records"], len(f_i)) + gs.shape, dtype=torch.float64, device=solver.backend.device)
             self.grids.append({"name": g["name"], "sampler": gs, "f_i": f_i, "f_e": f_e, "buf": buf, "t": []})
+        # surfaces (output key clip_surfaces, SolverKNPEMI.add_surface): per surface one built plan and one preallocated device tensor
+        # [records, fields, vertices]; a record is one gather launch, the tensors are read once in save_surfaces()
+        self.surfaces = []
+        if getattr(solver, "clip_surfaces", None) or getattr(solver, "surfaces", None):
+            from .surfaces import ClipSurface, SurfaceRecorder, named_functions
+            for g in solver.clip_surfaces:
+                S = ClipSurface(p, g["tags"], g["side"], g["origin"], g["normal"], g["boundary"])
+                self.surfaces.append(SurfaceRecorder(g["name"], S, *named_functions(p, g["fields"]), solver.surface_interval, solver.time_steps,
+                                                     self.prefix))
+            for name, S, fields, interval in solver.surfaces:
+                self.surfaces.append(SurfaceRecorder(name, S, *named_functions(p, fields), interval, solver.time_steps, self.prefix))
         # volume functionals (SolverKNPEMI.add_functional): one row of a preallocated device tensor per record, read once in
         # save_functionals()
         self.functionals = []
@@ -393,6 +404,8 @@ class RunOutput:
         for g in self.functionals:
             if i % g["interval"] == 0:
                 g["F"](out=g["buf"][i // g["interval"]])
+        for r in self.surfaces:
+            r.record(i, float(p.t.value))
         if self.fields_writer is not None:
             from .fields import record_arrays
             self.fields_writer.write(float(p.t.value), {name: record_arrays(F, nodal) for name, F, interval, nodal in self.fields
@@ -626,6 +639,11 @@ class RunOutput:
             np.save(out + f"grid_{g['name']}_tags.npy", np.ascontiguousarray(gs.cell_tag, dtype=np.int32))
             np.save(out + f"grid_{g['name']}_xyz.npy", gs.xyz)
             np.save(out + f"grid_{g['name']}_t.npy", np.array(g["t"]))
+
+    def save_surfaces(self):
+        """surface_<name>.xdmf / .h5 per recorded surface (one read-back each; a second call writes nothing)"""
+        for r in self.surfaces:
+            r.save()
 
     def save_functionals(self):
         """Per ``add_functional`` entry: functional_<name>.npy [records, n_tags, n_out] at steps 0, interval, 2 interval, ...;

@@ -446,6 +446,14 @@ class MixedDimensionalProblem(ABC):
             self.vol_i_g = volume(self.glia_tags)
             self.area_g_g = self.integrate_over_membrane(1.0, self.glia_tags)
 
+    def clip_surface(self, tags=None, side=None, origin=None, normal=None, boundary=True):
+        """a ``surfaces.ClipSurface``: the surface of the cells tagged ``tags`` (default: every intracellular tag; ``side`` 0 / 1:
+        all tags of a side) in the half-space normal . (x - origin) >= 0 (metres), cut open along the plane -- the reference's
+        ``threshold`` + ``clip`` --, or with ``boundary=False`` the exact slice alone.  Built once on the device (one read-back);
+        ``S(functions_i, functions_e)`` then evaluates nodal fields on it with one launch.  One rank only."""
+        from .surfaces import ClipSurface
+        return ClipSurface(self, tags, side, origin, normal, boundary)
+
     # ---------------------------------------------------------------- backend plumbing
     def create_backend(self):
         """Create the libknpemi_hip context for this rank's mesh (fails loudly without a HIP device)."""

@@ -89,6 +89,10 @@ class SolverKNPEMI:
     # lattice every sample_interval steps (grid_<name>.npy and its _tags, _xyz, _t files); empty: off
     sample_grids = ()
     sample_interval = 20
+    # output keys clip_surfaces (a list of named plane clips of tagged cells) / surface_interval (default: save_interval): the merged
+    # fields on each surface every surface_interval steps (surface_<name>.xdmf / .h5, cgx_hip/surfaces.py); empty: off
+    clip_surfaces = ()
+    surface_interval = 20
     tot_its = 0.0
     tot_assembly_time = 0.0
     tot_solver_time = 0.0
@@ -134,6 +138,10 @@ class SolverKNPEMI:
         from .output import parse_sample_grids
         self.sample_grids, self.sample_interval = parse_sample_grids(out, problem.local_mesh.coords.shape[1], float(problem.mesh_conversion_factor),
                                                                      int(self.save_interval), int(self.time_steps))
+        from .surfaces import parse_clip_surfaces
+        from .sampling import MERGED_FIELDS
+        self.clip_surfaces, self.surface_interval = parse_clip_surfaces(out, problem, int(self.save_interval), int(self.time_steps), MERGED_FIELDS)
+        self.surfaces = []         # add_surface(): (name, LevelSetSurface, fields, interval)
         self.out_file_prefix = problem.output_dir
         self.functionals = []      # add_functional(): (name, VolumeFunctional | MembraneFunctional, interval)
         self.fields = []           # add_field(): (name, CellField | FacetField, interval, nodal)
@@ -416,7 +424,7 @@ class SolverKNPEMI:
                                           or self.save_ion_budget or self.save_fluxes
                                           or self.membrane_potential_tags is not None or self.save_activation is not None
                                           or self.sample_grids or self.functionals
-                                          or self.fields) else None
+                                          or self.fields or self.clip_surfaces or self.surfaces) else None
         if self.output is not None:
             self.output.record(0)
 
@@ -583,6 +591,8 @@ class SolverKNPEMI:
             self.output.save_sample_grids()
         if self.functionals and self.output is not None:
             self.output.save_functionals()
+        if self.output is not None:
+            self.output.save_surfaces()
         if self.save_pngs and self.output is not None:
             self.output.figures()
         if self.save_dat:
@@ -624,6 +634,18 @@ class SolverKNPEMI:
             raise ValueError("interval must be at least 1")
         self.fields.append((name, F, int(interval), bool(nodal)))
 
+    def add_surface(self, name, S, fields=None, interval=None):
+        """Record nodal fields on the built surface ``S`` (cgx_hip/surfaces.py: ``ClipSurface``, ``IsoSurface``, ``LevelSetSurface``) at
+        step 0 and at every ``interval``-th step (default ``save_interval``), one gather launch per record and no host copy before the
+        end of the run: ``fields`` None for the merged ``Na, K, Cl, phi``, a list of those names, or a mapping name -> (function_i,
+        function_e).  The run ends with surface_<name>.xdmf / .h5: geometry, topology and the cell attributes ``tag`` and ``kind``
+        once, the node attributes per record.  solution.* and fields.* are not touched.  Call it before ``solve()`` / ``prepare()``."""
+        from .surfaces import check_add_surface
+        if getattr(self, "_prepared", False):
+            raise RuntimeError("add_surface() must be called before solve()")
+        taken = list(self.surfaces) + [(e["name"],) for e in self.clip_surfaces]
+        self.surfaces.append(check_add_surface(self, name, S, fields, interval, taken))
+
     def solve(self):
         self.prepare()
         try:
@@ -642,6 +664,8 @@ class SolverKNPEMI:
                 self.output.close_xdmf()
             if self.fields and getattr(self, "output", None) is not None:
                 self.output.close_fields()
+            if getattr(self, "output", None) is not None:
+                self.output.save_surfaces()            # a run that ended early keeps the records it made
 
     def potential_norms(self):
         """L2 norms of phi_i over Omega_i and phi_e over Omega_e (reference main.py:70-84)."""

@@ -4957,3 +4957,6 @@ int knp_amg_get_level_info(const knp_ctx* ctx, int32_t hier, int32_t level, int3
 
 // mesh refinement before a context exists: edge keys, midpoints, child cells and facets, prolongation of nodal fields (knp_refine_*)
 #include "knp_refine.inc"
+
+// level-set surfaces: clipped cell boundaries, slices and isolines as keyed vertices, one gather per record (knp_surface_*)
+#include "knp_surface.inc"
