@@ -56,6 +56,9 @@
  *   knp_functional_eval_items / knp_membrane_functional_eval_items / knp_project_apply
  *        a UFL expression projected or interpolated into a piecewise-constant or P1 space: its value on every cell or facet, and
  *        the measure-weighted average of those onto the vertices (current density, ion fluxes, channel currents as fields)
+ *   knp_functional_eval_load / knp_membrane_functional_eval_load / knp_scatter_apply / knp_rhs_add_load
+ *        dfx.fem.assemble_vector(dfx.fem.form(<UFL expression> * v * dx(tag) | dS(tag))) with a P1 test function v, and its
+ *        addition to the step's right-hand side: L += dt * inner(ion['f_i'], vki) * dxi (KNPEMIx_problem.py:613-614)
  *   knp_emi_*                        the EMI model (src/CGx/EMI): assemble_matrix_block / assemble_vector_block of the forms
  *                                    EMIx_problem.py:152-157, 215-217 and ksp.solve with KSPCG (EMIx_solver.py)
  *   knp_set_comm                     the MPI calls hidden in PETSc/DOLFINx (ghost updates
@@ -692,6 +695,42 @@ int knp_project_apply(knp_ctx* ctx, int32_t id, const double* values /* device [
                       double* out /* device [n_out*n_vertices] */);
 int knp_project_get_info(const knp_ctx* ctx, int32_t id, int32_t* out /* host [n] */, int n);
 int knp_project_destroy(knp_ctx* ctx, int32_t id);
+/* Linear forms: int f v dx(tag) and int g v dS(tag) against the P1 test functions, one number per vertex, for any program of a
+ * functional; and their addition to the right-hand side of a step.
+ * knp_functional_eval_load / knp_membrane_functional_eval_load: for a plan of knp_functional_create /
+ *   knp_membrane_functional_create, with nv = dim+1 vertices of a cell or dim of a facet,
+ *     out[(i*nv + a)*n_out + j] = sum_q (measure_i q_w[q] lambda_a(q)) OUT_j(program at point q of item i),
+ *   q ascending: the item's element vector, i the item's place in the list given at create, a the local vertex in the order of the
+ *   mesh's cell (the facet's vertices of the Gamma list), lambda_a(q) the a-th barycentric coordinate of point q.  Item-major, so
+ *   that knp_scatter_apply finds the n_out numbers of an entry side by side.  The kernel is the functional's own with a third end:
+ *   the same loads, geometry, derivative slots and normal modes, the interpreter's register file in LDS; the tag keys are not read
+ *   and the segmented scan's LDS is not needed.  Enqueued on the library's stream; never waits for the device; the constants of the
+ *   plan travel as kernel arguments.  A plan without items is a successful no-op.  KNP_E_ARG with nothing launched: an unknown id,
+ *   null fields or out, a null pointer of a slot the code reads.
+ * Scatter plans: sum-only gathers that belong to the context like projections (ids of their own; a destroyed id is reused;
+ * knp_destroy frees the plans that are left).
+ * knp_scatter_create: from the vertices of n_items items (nv each) it builds the inverted index on the host: per vertex the entries
+ *   (i, a) with item_vertices[i*nv + a] == v, ascending in i.  Synchronous; 4 bytes per entry and 12 per vertex of device memory.
+ *   KNP_E_ARG and no plan: a null argument, nv outside 2 .. 4, a vertex outside 0 .. n_vertices-1, an item that lists a vertex twice.
+ * knp_scatter_apply: out[j*n_vertices + v] = sum over v's entries, in that order, of values[(i*nv + a)*n_out + j]; 0 where the list
+ *   is empty.  The kernels, the lane rule and the split rule are knp_project_apply's with weight 1 and no division: no atomics, the
+ *   same bits on every run.  Enqueued on the library's stream; never waits for the device.  KNP_E_ARG with nothing launched: an
+ *   unknown id, n_out outside 1 .. 3, null values or out.
+ * knp_scatter_get_info: the slots of knp_project_get_info (KNP_PI_*), for a scatter plan.
+ * knp_scatter_destroy: frees the plan (waits for the stream first).
+ * knp_rhs_add_load: b[4*node + field] += scale * load[vertex of node] on the owned nodes of `side`; every other entry of b is left
+ *   alone.  One lane per owned node, on the library's stream behind knp_assemble_rhs; never waits for the device.  KNP_E_ARG with
+ *   nothing launched: a field outside 0 .. 3, a side outside 0 .. 1, a null pointer.  One GPU only: KNP_E_STATE on a context with
+ *   ghost nodes. */
+int knp_functional_eval_load(knp_ctx* ctx, int32_t id, const knp_fields* fields, double* out /* device [n_items*nv*n_out] */);
+int knp_membrane_functional_eval_load(knp_ctx* ctx, int32_t id, const knp_fields* fields, double* out /* device [n_items*nv*n_out] */);
+int knp_scatter_create(knp_ctx* ctx, int32_t n_items, int32_t nv, const int32_t* item_vertices /* host [n_items*nv] */, int32_t* id /* host */);
+int knp_scatter_apply(knp_ctx* ctx, int32_t id, const double* values /* device [n_items*nv*n_out] */, int32_t n_out /* 1..3 */,
+                      double* out /* device [n_out*n_vertices] */);
+int knp_scatter_get_info(const knp_ctx* ctx, int32_t id, int32_t* out /* host [n] */, int n);
+int knp_scatter_destroy(knp_ctx* ctx, int32_t id);
+int knp_rhs_add_load(knp_ctx* ctx, int32_t field /* 0..2 ion, 3 potential */, int32_t side /* 0 intra, 1 extra */, double scale,
+                     const double* load /* device [n_vertices] */, double* b /* device [n_dof_local] */);
 
 /* ---- the EMI model: two potentials with constant conductivities, ONE unknown per node (reference src/CGx/EMI) ----
  * Unknown n is node n of knp_get_layout; every vector is a device array of n_nodes_owned doubles.  One GPU only: every call

@@ -163,6 +163,13 @@ SIGNATURES = {
     "knp_project_apply": (C.c_int, [vp, C.c_int32, vp, C.c_int32, C.c_double, vp]),
     "knp_project_get_info": (C.c_int, [vp, C.c_int32, i32p, C.c_int]),
     "knp_project_destroy": (C.c_int, [vp, C.c_int32]),
+    "knp_functional_eval_load": (C.c_int, [vp, C.c_int32, C.POINTER(Fields), vp]),
+    "knp_membrane_functional_eval_load": (C.c_int, [vp, C.c_int32, C.POINTER(Fields), vp]),
+    "knp_scatter_create": (C.c_int, [vp, C.c_int32, C.c_int32, i32p, i32p]),
+    "knp_scatter_apply": (C.c_int, [vp, C.c_int32, vp, C.c_int32, vp]),
+    "knp_scatter_get_info": (C.c_int, [vp, C.c_int32, i32p, C.c_int]),
+    "knp_scatter_destroy": (C.c_int, [vp, C.c_int32]),
+    "knp_rhs_add_load": (C.c_int, [vp, C.c_int32, C.c_int32, C.c_double, vp, vp]),
     "knp_emi_setup": (C.c_int, [vp, C.c_double, C.c_double, C.c_double, C.c_double]),
     "knp_emi_get_csr": (C.c_int, [vp, i32p, i32p, f64p]),
     "knp_emi_set_dirichlet": (C.c_int, [vp, C.c_int32, i32p]),

@@ -424,6 +424,19 @@ class ProblemEMI(MixedDimensionalProblem):
         from .fields import FacetField
         return FacetField(self, expr, tags, degree, name)
 
+    def assemble_vector(self, integrand_i=None, integrand_e=None, tags=None, degree=2):
+        """``ProblemKNPEMI.assemble_vector`` for the EMI model: ``int integrand v dx(tags)`` per vertex against the P1 test
+        functions, NumPy [2, n_out, n_vertices] (every Function is an aux field).  Needs ``setup_bilinear_form()`` first.  There
+        are no step hooks on this problem: its right-hand side is projected and Dirichlet-lifted inside the library's assembly."""
+        from .linear_forms import assemble_vector
+        return assemble_vector(self, integrand_i, integrand_e, tags, degree)
+
+    def assemble_vector_membrane(self, integrand, tags=None, degree=10):
+        """``ProblemKNPEMI.assemble_vector_membrane`` for the EMI model: ``int integrand v dS(tags)`` per vertex, NumPy
+        [n_out, n_vertices]"""
+        from .linear_forms import assemble_vector_membrane
+        return assemble_vector_membrane(self, integrand, tags, degree)
+
     def activation_map(self, threshold, repolarisation_threshold=None, tags=None):
         """an ``activation.ActivationMap`` of ``phi_M`` on the membranes tagged ``tags`` (default every tag of ``gamma_tags``), armed
         now: call its ``update()`` after every step, then ``result()``, ``velocity()``, ``per_tag()``"""

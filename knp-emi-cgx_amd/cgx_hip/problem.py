@@ -927,6 +927,40 @@ class ProblemKNPEMI(MixedDimensionalProblem):
         from .fields import FacetField
         return FacetField(self, expr, tags, degree, name)
 
+    def assemble_vector(self, integrand_i=None, integrand_e=None, tags=None, degree=2):
+        """``dfx.fem.assemble_vector(dfx.fem.form(integrand * v * dx(tags)))`` with a P1 test function ``v``: NumPy
+        [2, n_out, n_vertices], row 0 the intracellular cells' integrals per vertex and row 1 the extracellular ones', 0 where a vertex
+        has no listed cell of that side.  Expressions, ``tags`` and refusals are ``assemble_scalar``'s; ``degree`` counts the test
+        function in.  Keep a ``linear_forms.VolumeLinearForm`` to assemble again or to stay on the device."""
+        from .linear_forms import assemble_vector
+        return assemble_vector(self, integrand_i, integrand_e, tags, degree)
+
+    def assemble_vector_membrane(self, integrand, tags=None, degree=10):
+        """``dfx.fem.assemble_vector(dfx.fem.form(integrand * v * dS(tags)))``: NumPy [n_out, n_vertices], 0 away from the listed
+        membranes.  Expressions, ``tags`` and refusals are ``assemble_scalar_membrane``'s."""
+        from .linear_forms import assemble_vector_membrane
+        return assemble_vector_membrane(self, integrand, tags, degree)
+
+    def add_source(self, field, expr_i=None, expr_e=None, tags=None, degree=2):
+        """Add ``dt * int expr v dx(tags)`` to the right-hand side rows of ``field`` ('Na' | 'K' | 'Cl' | 'phi' or 0..3) at every
+        step from now on: ``expr_i`` on the intracellular nodes, ``expr_e`` on the extracellular ones (``tags``: default every cell
+        tag of the sides that have an expression).  For an ion this is the reference's ``L += dt * inner(ion['f_i'], vki) * dxi``
+        (KNPEMIx_problem.py:613-614); for 'phi' it is a plain addition -- the reference's MMS potential sources enter its form
+        with a minus sign, so pass the negated expression to restate them.  The expression is evaluated on the device when
+        ``SolverKNPEMI.assemble()`` runs, at the new time ``t`` and the previous step's solution: one load launch, one gather and
+        one add per side, no host copy.  Callable before or between steps.  Refused: an unknown field, more than one rank, an
+        expression that reads a solution function of the other side, more than one expression per side.  Returns a
+        ``linear_forms.Source``: ``h.enabled = False`` skips it, ``h.remove()`` takes it off."""
+        from .linear_forms import add_source
+        return add_source(self, field, expr_i, expr_e, tags, degree)
+
+    def add_membrane_source(self, field, side, expr, tags=None, degree=10):
+        """Add ``dt * int expr v dS(tags)`` to the rows of ``field`` on the nodes of ``side`` ('i' | 'e') at every step from now
+        on; ``expr`` is a membrane integrand (restrictions, ``fem.FacetNormal``, ``fem.NormalDerivative``; it may read both sides),
+        ``tags`` as ``assemble_scalar_membrane`` takes them.  Otherwise as ``add_source``."""
+        from .linear_forms import add_membrane_source
+        return add_membrane_source(self, field, side, expr, tags, degree)
+
     def activation_map(self, threshold, repolarisation_threshold=None, tags=None):
         """an ``activation.ActivationMap`` of ``phi_m_prev`` on the membranes tagged ``tags`` (default every tag of ``gamma_tags``),
         armed now: call its ``update()`` after every step, then ``result()``, ``velocity()``, ``per_tag()``"""

@@ -207,6 +207,10 @@ class SolverKNPEMI:
                 p._mms_asm = MMSAssembler(p)
             extra = p._mms_asm.rhs_vector(be.node_i, be.node_e, be.n_dof_local)
             be.b += torch.as_tensor(extra, dtype=torch.float64, device=be.device)
+        if getattr(p, "_sources", None):
+            # the sources of add_source / add_membrane_source: dt * int f v, evaluated on the device on this chain's stream
+            from .linear_forms import apply_sources
+            apply_sources(p, be)
         be.apply_dirichlet_rhs()
         if self._b_is_final:
             if self._flexible:

@@ -18,7 +18,9 @@
 //                   the per-tag reduction, the diagnostics' own: diag_chunk_partials, and on the host k_diag_combine and, for the tags of
 //                   more than FN_WAVE_CHUNKS chunks, k_diag_combine_long.  No atomics: the same inputs give the same bits on every run.
 //                   With ITEMS it ends in a plain store instead (knp_fields.inc): the item's mean sum_q q_w[q] OUT_j, measure not
-//                   applied, at dst[i n_out + j] of every live lane.
+//                   applied, at dst[i n_out + j] of every live lane.  With LOAD (knp_fields.inc) every quadrature value is weighted
+//                   with the P1 test function of each of the item's vertices, measure q_w[q] lambda_a OUT_j, and every live lane stores
+//                   its NV x NOUT sums at dst[(i NV + a) n_out + j]: the element vectors of a linear form.
 //   fn_create, fn_of, fn_set_constants, fn_eval, fn_destroy, fn_free   the plan's life, with the kind's name in the error texts.
 // The volume kind's own:
 //   k_functional    one cell per lane, FN_BT cells per block.  The lane loads its cell's vertices and coordinates and forms |T|.  A slot
@@ -29,6 +31,7 @@ static constexpr int FN_BT = 128;              // items per block: the interpret
 static constexpr int FN_WAVE_CHUNKS = 64;      // longer tags take the workgroup combine
 // which field slots a program reads: bit j k_i[j], bit 3 + j k_e[j], bit 6 phi_m, bit 7 + k aux[k]; from bit 15 up the kind's own
 static constexpr unsigned FN_KI = 1u, FN_KE = 1u << 3, FN_PHIM = 1u << 6, FN_AUX = 1u << 7, FN_DERIV = 1u << 15;
+enum FnEnd { FN_TAGS, FN_ITEMS, FN_LOAD };     // how fn_integrate ends: the per-tag reduction, the item's mean, the item's load vector
 static constexpr int FN_NORMAL = 8;            // slot modes from here up have no field behind them (a membrane plan's normal components)
 struct FnBind {
     unsigned need;
@@ -86,15 +89,21 @@ __device__ __forceinline__ void fn_load_fields(const FieldPtrs& f, const FnBind&
 // Per quadrature point: interpolate the values and the coordinates x of the item's vertices, run the interpreter and add
 // meas q_w[q] OUT_j, every output on its own; then the diagnostics' per-tag reduction of the block (diag_chunk_partials).  The order of
 // a in the interpolation sums and of q in the accumulation fixes the bits.  ITEMS: the weight is q_w[q] alone and the end is one store
-// per live lane, dst = the caller's [n][NOUT]; key is not read.
-template <int DIM, int NV, int NOUT, bool ITEMS>
+// per live lane, dst = the caller's [n][NOUT]; key is not read.  LOAD: NV x NOUT sums, acc[a][j] += (meas q_w[q] lam[a]) OUT_j in the same
+// order of q, and the end is the store of all of them, dst = the caller's [n][NV][NOUT]: item-major, so that the gather of
+// knp_scatter_apply finds the NOUT numbers of an entry (i, a) side by side; key is not read, and there is no reduction.
+template <int DIM, int NV, int NOUT, FnEnd END>
 __device__ __forceinline__ void fn_integrate(const FnLane& L, int n, const int32_t* __restrict__ key, const FnValues<NV>& U,
                                              const double (*x)[DIM], const FnBind& B, int n_q, const double* __restrict__ qp,
                                              const double* __restrict__ qw, double meas, const int32_t* __restrict__ code, int n_instr,
                                              double* __restrict__ partial) {
-    double acc[NOUT];
+    constexpr bool ITEMS = END == FN_ITEMS;
+    constexpr int NA = END == FN_LOAD ? NV : 1;      // accumulators per output
+    double acc[NA][NOUT];
 #pragma unroll
-    for (int j = 0; j < NOUT; ++j) acc[j] = 0.0;
+    for (int a = 0; a < NA; ++a)
+#pragma unroll
+        for (int j = 0; j < NOUT; ++j) acc[a][j] = 0.0;
     for (int q = 0; q < n_q; ++q) {
         double lam[NV];
 #pragma unroll
@@ -133,24 +142,40 @@ __device__ __forceinline__ void fn_integrate(const FnLane& L, int n, const int32
         }
         run_program<1, FN_BT>(code, n_instr, L.sk, kiq, keq, phq, auxq, xq, Iout, L.reg);
         const double w = ITEMS ? qw[q] : qw[q] * meas;
+        if constexpr (END == FN_LOAD) {
 #pragma unroll
-        for (int j = 0; j < NOUT; ++j) acc[j] += w * Iout[0][j];
+            for (int a = 0; a < NV; ++a) {
+                const double wa = w * lam[a];
+#pragma unroll
+                for (int j = 0; j < NOUT; ++j) acc[a][j] += wa * Iout[0][j];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < NOUT; ++j) acc[0][j] += w * Iout[0][j];
+        }
     }
-    if constexpr (ITEMS) {
+    if constexpr (END == FN_LOAD) {
         if (L.live) {
 #pragma unroll
-            for (int j = 0; j < NOUT; ++j) partial[(size_t)L.i * NOUT + j] = acc[j];
+            for (int a = 0; a < NV; ++a)
+#pragma unroll
+                for (int j = 0; j < NOUT; ++j) partial[((size_t)L.i * NV + a) * NOUT + j] = acc[a][j];
+        }
+    } else if constexpr (ITEMS) {
+        if (L.live) {
+#pragma unroll
+            for (int j = 0; j < NOUT; ++j) partial[(size_t)L.i * NOUT + j] = acc[0][j];
         }
     } else {
         DiagSum<NOUT> s;
 #pragma unroll
-        for (int j = 0; j < NOUT; ++j) s.v[j] = acc[j];
+        for (int j = 0; j < NOUT; ++j) s.v[j] = acc[0][j];
         diag_chunk_partials<DiagSum<NOUT>, FN_BT>(L.live ? key[L.i] : -1, L.live, L.i == n - 1, s, partial);
     }
 }
 
 // ---- the volume kind's own: the cell load, |T|, grad(lambda) and the derivative slots ---------------------------------------------
-template <int DIM, int NOUT, bool ITEMS = false>
+template <int DIM, int NOUT, FnEnd END = FN_TAGS>
 __global__ void __launch_bounds__(FN_BT) k_functional(int n, const int32_t* __restrict__ item, const int32_t* __restrict__ key,
                                                       const int32_t* __restrict__ cells, const double* __restrict__ coords, int n_q,
                                                       const double* __restrict__ qb, const double* __restrict__ qw, FieldPtrs f, FnBind B,
@@ -198,7 +223,7 @@ __global__ void __launch_bounds__(FN_BT) k_functional(int n, const int32_t* __re
             U.av[k][0] = d;
         }
     }
-    fn_integrate<DIM, DIM + 1, NOUT, ITEMS>(L, n, key, U, x, B, n_q, qb, qw, vol, code, n_instr, partial);
+    fn_integrate<DIM, DIM + 1, NOUT, END>(L, n, key, U, x, B, n_q, qb, qw, vol, code, n_instr, partial);
 }
 
 // ---- the plan lifecycle both kinds share.  A kind is its name in the error texts and its table of the context: the ids of the two
@@ -301,14 +326,16 @@ static int fn_set_constants(knp_ctx* ctx, const FnKind& kind, int32_t id, int32_
     return KNP_OK;
 }
 
-// Evaluation of either kind: binds the fields the program reads, then launch(D, NOUT, ITEMS, P, f, B, K, lds, dst) is the kind's kernel
-// over the plan's map, and the combines write out.  ITEMS (knp_fields.inc): the kernel stores every item's mean straight into out
-// (dst = out, [n][n_out] in the plan's item order) and there is no combine; otherwise dst is the map's partials.
-template <bool ITEMS, class Launch>
+// Evaluation of either kind: binds the fields the program reads, then launch(D, NOUT, END, P, f, B, K, lds, dst) is the kind's kernel
+// over the plan's map, and the combines write out.  FN_ITEMS / FN_LOAD (knp_fields.inc): the kernel stores every item's mean, or its
+// load vector, straight into out (dst = out, [n][n_out] or [n][nv][n_out] in the plan's item order) and there is no combine; otherwise
+// dst is the map's partials.
+template <FnEnd END, class Launch>
 static int fn_eval(knp_ctx* ctx, const FnKind& kind, int32_t id, const knp_fields* fields, double* out, Launch launch) {
     KCHK(fn_of(ctx, kind, id));
     const KnpFunctional& P = kind.plans[(size_t)id];
     const KnpDiagMap& m = P.map;
+    constexpr bool ITEMS = END != FN_TAGS;      // the ends that store per item
     if (ITEMS ? m.n == 0 : m.n_tags == 0) return KNP_OK;
     if (!fields || !out) { ctx->err = std::string(kind.name) + ": null fields or null output buffer"; return KNP_E_ARG; }
     FieldPtrs f;
@@ -334,7 +361,7 @@ static int fn_eval(knp_ctx* ctx, const FnKind& kind, int32_t id, const knp_field
         for (int i = 0; i < KNP_DIAG_MAX_CONSTS; ++i) K.v[i] = i < P.n_consts ? P.consts[i] : 0.0;
         const size_t lds = (size_t)std::max(P.n_regs, 1) * FN_BT * sizeof(double);   // <= 48 registers: 48 KiB
         double* dst = ITEMS ? out : m.d_partial;
-        const std::integral_constant<bool, ITEMS> items;
+        const std::integral_constant<FnEnd, END> items;
         by_dim(ctx->g.dim, [&](auto D) {
             if (P.n_out == 1) launch(D, std::integral_constant<int, 1>(), items, P, f, B, K, lds, dst);
             else if (P.n_out == 2) launch(D, std::integral_constant<int, 2>(), items, P, f, B, K, lds, dst);
@@ -374,9 +401,9 @@ static bool functional_flat_cell(const std::vector<int32_t>& cells, const std::v
 }
 
 // the volume kind's launch, of either end (fn_eval)
-template <bool ITEMS>
+template <FnEnd END>
 static int functional_eval(knp_ctx* ctx, int32_t id, const knp_fields* fields, double* out) {
-    return fn_eval<ITEMS>(ctx, fn_volume(ctx), id, fields, out,
+    return fn_eval<END>(ctx, fn_volume(ctx), id, fields, out,
                           [&](auto D, auto NOUT, auto I, const KnpFunctional& P, const FieldPtrs& f, const FnBind& B, const DiagConsts& K, size_t lds,
                               double* dst) {
                               const KnpDiagMap& m = P.map;
@@ -418,7 +445,7 @@ int knp_functional_set_constants(knp_ctx* ctx, int32_t id, int32_t n_consts, con
 
 int knp_functional_eval(knp_ctx* ctx, int32_t id, const knp_fields* fields, double* out) {
     CHECK_CTX(ctx);
-    return functional_eval<false>(ctx, id, fields, out);
+    return functional_eval<FN_TAGS>(ctx, id, fields, out);
 }
 
 int knp_functional_destroy(knp_ctx* ctx, int32_t id) {

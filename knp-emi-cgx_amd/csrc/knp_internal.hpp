@@ -496,6 +496,7 @@ struct knp_ctx {
     std::vector<KnpFunctional> functionals;    // knp_functional_create: likewise
     std::vector<KnpFunctional> membrane_functionals;   // knp_membrane_functional_create: likewise
     std::vector<KnpProjection> projections;    // knp_project_create: likewise
+    std::vector<KnpProjection> scatters;       // knp_scatter_create: likewise (sum-only plans: no d_meas, no d_inv; d_item holds i nv + a)
     // profiling
     int prof_on = 0;
     std::vector<hipEvent_t> prof_pool;   // recycled timing events

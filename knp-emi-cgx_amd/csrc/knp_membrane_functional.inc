@@ -24,7 +24,7 @@ static constexpr int MF_DN_I = 6, MF_DN_E = 7, MF_NORMAL = FN_NORMAL;      // sl
 static inline bool mf_mode_ext(int m) { return (m >= 3 && m < MF_DN_I) || m == MF_DN_E; }            // reads the extracellular cell
 static inline bool mf_mode_int(int m) { return (m >= 0 && m < 3) || m == MF_DN_I || m == MF_DN_E || m >= MF_NORMAL; }   // the normal is the intracellular cell's
 
-template <int DIM, int NOUT, bool ITEMS = false>
+template <int DIM, int NOUT, FnEnd END = FN_TAGS>
 __global__ void __launch_bounds__(FN_BT) k_membrane_functional(int n, const int32_t* __restrict__ item, const int32_t* __restrict__ key,
                                                                const int4* __restrict__ rec, const double* __restrict__ fmeas,
                                                                const double* __restrict__ coords, int n_q, const double* __restrict__ qp,
@@ -114,7 +114,7 @@ __global__ void __launch_bounds__(FN_BT) k_membrane_functional(int n, const int3
             U.av[k][0] = d;
         }
     }
-    fn_integrate<DIM, DIM, NOUT, ITEMS>(L, n, key, U, x, B, n_q, qp, qw, meas, code, n_instr, partial);
+    fn_integrate<DIM, DIM, NOUT, END>(L, n, key, U, x, B, n_q, qp, qw, meas, code, n_instr, partial);
 }
 
 // the records of k_membrane_functional for the facets of a map, in map order; counts the facets whose extracellular cell does not hold
@@ -152,9 +152,9 @@ static void membrane_functional_records(const KnpHostGraph& g, const std::vector
 }
 
 // the membrane kind's launch, of either end (fn_eval)
-template <bool ITEMS>
+template <FnEnd END>
 static int membrane_functional_eval(knp_ctx* ctx, int32_t id, const knp_fields* fields, double* out) {
-    return fn_eval<ITEMS>(ctx, fn_membrane(ctx), id, fields, out,
+    return fn_eval<END>(ctx, fn_membrane(ctx), id, fields, out,
                           [&](auto D, auto NOUT, auto I, const KnpFunctional& P, const FieldPtrs& f, const FnBind& B, const DiagConsts& K, size_t lds,
                               double* dst) {
                               const KnpDiagMap& m = P.map;
@@ -206,7 +206,7 @@ int knp_membrane_functional_set_constants(knp_ctx* ctx, int32_t id, int32_t n_co
 
 int knp_membrane_functional_eval(knp_ctx* ctx, int32_t id, const knp_fields* fields, double* out) {
     CHECK_CTX(ctx);
-    return membrane_functional_eval<false>(ctx, id, fields, out);
+    return membrane_functional_eval<FN_TAGS>(ctx, id, fields, out);
 }
 
 int knp_membrane_functional_destroy(knp_ctx* ctx, int32_t id) {
