@@ -137,7 +137,8 @@ enum {
     KNP_OP_SEL = 26,   /* dst = (reg[a] != 0) ? reg[b] : reg[dst]   (dst preloaded with the else-value) */
     KNP_OP_OUT = 27,   /* I_ch^a += reg[b] */
     KNP_OP_MOV = 28,
-    KNP_OP_POWI = 29   /* dst = reg[a]^b with integer literal b */
+    KNP_OP_POWI = 29,  /* dst = reg[a]^b with integer literal b */
+    KNP_OP_SIN = 30, KNP_OP_COS = 31, KNP_OP_TANH = 32   /* unary functions: dst = f(reg[a]) */
 };
 
 typedef struct knp_ctx knp_ctx;

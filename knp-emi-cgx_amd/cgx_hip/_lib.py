@@ -27,6 +27,9 @@ PC_NONE, PC_VBJACOBI, PC_AMG, PC_AMG_BT, PC_AMG_LT = 0, 1, 2, 3, 4
 OPS = dict(CONST=0, KI=1, KE=2, PHIM=3, AUX=4, X=5, ADD=6, SUB=7, MUL=8, DIV=9, NEG=10, POW=11, LN=12,
            EXP=13, SQRT=14, MAX=15, MIN=16, ABS=17, LT=18, GT=19, LE=20, GE=21, EQ=22, AND=23, OR=24,
            NOT=25, SEL=26, OUT=27, MOV=28, POWI=29)
+# the unary function block that follows the base set (dst = f(reg[a])); the compiler and the interpreters look names up in ALL_OPS
+FUNC_OPS = dict(SIN=30, COS=31, TANH=32)
+ALL_OPS = {**OPS, **FUNC_OPS}
 
 REASONS = {2: "CONVERGED_RTOL", 3: "CONVERGED_ATOL", -3: "DIVERGED_ITS", -4: "DIVERGED_DTOL",
            -9: "DIVERGED_NANORINF", 0: "ITERATING"}

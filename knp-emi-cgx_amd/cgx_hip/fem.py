@@ -22,7 +22,7 @@ import numbers
 import numpy as np
 import torch
 
-from ._lib import KNP_MAX_AUX, KNP_MAX_PROG_REGS, OPS
+from ._lib import ALL_OPS, FUNC_OPS, KNP_MAX_AUX, KNP_MAX_PROG_REGS, OPS  # noqa: F401  (OPS: the base opcode table, part of this module's interface)
 
 
 # ------------------------------------------------------------------------------------------
@@ -199,6 +199,9 @@ def as_expr(v):
 def ln(x): return Op("LN", (as_expr(x),))
 def exp(x): return Op("EXP", (as_expr(x),))
 def sqrt(x): return Op("SQRT", (as_expr(x),))
+def sin(x): return Op("SIN", (as_expr(x),))
+def cos(x): return Op("COS", (as_expr(x),))
+def tanh(x): return Op("TANH", (as_expr(x),))
 def max_value(a, b): return Op("MAX", (as_expr(a), as_expr(b)))
 def min_value(a, b): return Op("MIN", (as_expr(a), as_expr(b)))
 def lt(a, b): return Op("LT", (as_expr(a), as_expr(b)))
@@ -253,6 +256,7 @@ def dot(a, b):
     return inner(a, b)
 
 
+pi = math.pi
 max = max_value      # noqa: A001  (the reference spells it ufl.max / ufl.min)
 min = min_value      # noqa: A001
 
@@ -415,25 +419,25 @@ def compile_program(outputs, field_roles, aux_functions=None, aux_derivs=None, f
         r = free.pop()
         reg[i] = r
         if op in ("CONST", "KI", "KE", "AUX", "X"):
-            code.append((OPS[op], r, imm, 0))
+            code.append((ALL_OPS[op], r, imm, 0))
         elif op == "PHIM":
-            code.append((OPS[op], r, 0, 0))
+            code.append((ALL_OPS[op], r, 0, 0))
         elif op == "POWI":
-            code.append((OPS[op], r, reg[args[0]], imm))
+            code.append((ALL_OPS[op], r, reg[args[0]], imm))
         elif op == "SEL":
             c, t, f = args
-            code.append((OPS["MOV"], r, reg[f], 0))
-            code.append((OPS["SEL"], r, reg[c], reg[t]))
+            code.append((ALL_OPS["MOV"], r, reg[f], 0))
+            code.append((ALL_OPS["SEL"], r, reg[c], reg[t]))
             for a in releasable:
                 free.append(reg[a])
         elif len(args) == 1:
-            code.append((OPS[op], r, reg[args[0]], 0))
+            code.append((ALL_OPS[op], r, reg[args[0]], 0))
         else:
-            code.append((OPS[op], r, reg[args[0]], reg[args[1]]))
+            code.append((ALL_OPS[op], r, reg[args[0]], reg[args[1]]))
         if last_use[i] == -1:          # dead value
             free.append(r)
     for k, oid in enumerate(out_ids):
-        code.append((OPS["OUT"], 0, k, reg[oid]))
+        code.append((ALL_OPS["OUT"], 0, k, reg[oid]))
     return ProgramSpec(np.array(code, dtype=np.int32).reshape(-1, 4), consts, aux_functions, aux_derivs)
 
 
@@ -571,6 +575,9 @@ def evaluate_numpy(e, env):
     if op == "LN": return np.log(a[0])
     if op == "EXP": return np.exp(a[0])
     if op == "SQRT": return np.sqrt(a[0])
+    if op == "SIN": return np.sin(a[0])
+    if op == "COS": return np.cos(a[0])
+    if op == "TANH": return np.tanh(a[0])
     if op == "MAX": return np.maximum(a[0], a[1])
     if op == "MIN": return np.minimum(a[0], a[1])
     if op == "LT": return (a[0] < a[1]) * 1.0
@@ -590,7 +597,7 @@ def interpret_program(spec: ProgramSpec, ki, ke, phim, aux, xq):
     consts = spec.constants()
     reg = [0.0] * KNP_MAX_PROG_REGS
     out = [0.0, 0.0, 0.0]
-    inv = {v: k for k, v in OPS.items()}
+    inv = {v: k for k, v in ALL_OPS.items()}
     for op, d, a, b in spec.code.tolist():
         name = inv[op]
         if name == "CONST": reg[d] = consts[a]
@@ -609,6 +616,9 @@ def interpret_program(spec: ProgramSpec, ki, ke, phim, aux, xq):
         elif name == "LN": reg[d] = np.log(reg[a])
         elif name == "EXP": reg[d] = np.exp(reg[a])
         elif name == "SQRT": reg[d] = np.sqrt(reg[a])
+        elif name == "SIN": reg[d] = np.sin(reg[a])
+        elif name == "COS": reg[d] = np.cos(reg[a])
+        elif name == "TANH": reg[d] = np.tanh(reg[a])
         elif name == "MAX": reg[d] = np.maximum(reg[a], reg[b])
         elif name == "MIN": reg[d] = np.minimum(reg[a], reg[b])
         elif name == "ABS": reg[d] = np.abs(reg[a])

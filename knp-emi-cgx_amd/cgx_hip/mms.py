@@ -4,9 +4,14 @@ Mirrors reference src/CGx/utils/setup_mms.py (``ExactSolutionsKNPEMI``: exact so
 and the MMS branches of src/CGx/KNPEMI/KNPEMIx_problem.py (:109-134 Dirichlet data, :363-431 initial data,
 :616-651 extra terms of L, :746-805 unit parameters, :845-907 error norms).
 
-This is verification tooling, not the timed hot path: the analytic source integrals are evaluated on the host
-with NumPy once per step and added to the right-hand side that the HIP kernels assembled; the Dirichlet rows
-themselves are applied by the library (``knp_set_dirichlet``).  SymPy replaces UFL's symbolic differentiation.
+This is verification tooling: by default the analytic source integrals are evaluated on the host with NumPy once per
+step and added to the right-hand side that the HIP kernels assembled; the Dirichlet rows themselves are applied by the
+library (``knp_set_dirichlet``).  SymPy replaces UFL's symbolic differentiation.
+
+``MMS_test: {..., device: true}`` moves the per-step work to the device: ``to_fem`` turns the SymPy terms into
+expressions of cgx_hip/fem.py (sin, cos and exp are opcodes of the membrane bytecode), ``device_source_terms`` states
+the sixteen terms of ``MMSAssembler.rhs_vector`` as step sources (``add_source`` / ``add_membrane_source``), and
+``DeviceErrors`` integrates the squared errors with two volume functionals.  The host path stays the reference of both.
 """
 from __future__ import annotations
 
@@ -201,4 +206,142 @@ class MMSAssembler:
                 uq = np.einsum("qa,ca->cq", self.qp, uh[self.cells[sel]])
                 ex = p.M.evaluate(p.exact_sols[f"{nm}_{r}"], self.xq_c[sel], t)
                 out.append(math.sqrt(float((self.vol[sel][:, None] * self.qw[None, :] * (uq - ex) ** 2).sum())))
+        return out
+
+
+# ------------------------------------------------------------------------------------------ the device path (MMS_test: device)
+def to_fem(expr, problem, _memo=None):
+    """A SymPy term of ``ExactSolutionsKNPEMI`` as an expression of cgx_hip/fem.py: x, y, z are the spatial coordinates, t the
+    problem's ``t`` Constant (read anew whenever a program's constants are refreshed), n_x, n_y, n_z the components of the facet
+    normal restricted to ('+') -- out of the intracellular cell, the normal of ``MMSAssembler``.  Numbers and pi become literals,
+    an integer exponent ``**int`` (KNP_OP_POWI), any other one KNP_OP_POW; sin, cos and exp their opcodes.  The tree is taken as it
+    is (no ``expand()``); equal sub-trees become one node."""
+    from . import fem
+    M = problem.M
+    memo = {} if _memo is None else _memo
+    if not memo:
+        x = fem.SpatialCoordinate(problem.mesh)
+        n = fem.FacetNormal(problem.mesh)
+        for a in range(M.dim):
+            memo[M.X[a]] = x[a]
+            memo[M.nsym[a]] = n[a]("+")
+        memo[M.ts] = problem.t
+    funcs = {sy.sin: fem.sin, sy.cos: fem.cos, sy.exp: fem.exp}
+
+    def fold(args, op):
+        out = args[0]
+        for a in args[1:]:
+            out = op(out, a)
+        return out
+
+    def visit(e):
+        if e in memo:
+            return memo[e]
+        if e.is_Integer:
+            r = fem.Literal(float(int(e)))
+        elif e.is_Rational:
+            r = fem.Literal(int(e.p) / int(e.q))
+        elif e is sy.pi:
+            r = fem.Literal(math.pi)
+        elif e.is_Float:
+            r = fem.Literal(float(e))
+        elif e.is_Symbol:
+            raise ValueError(f"unknown symbol {e} in an MMS term")
+        elif e.is_Add:
+            r = fold([visit(a) for a in e.args], lambda u, v: u + v)
+        elif e.is_Mul:
+            r = fold([visit(a) for a in e.args], lambda u, v: u * v)
+        elif e.is_Pow:
+            base, ex = e.args
+            r = visit(base) ** int(ex) if ex.is_Integer else fem.Op("POW", (visit(base), visit(ex)))
+        elif e.func in funcs:
+            r = funcs[e.func](visit(e.args[0]))
+        else:
+            raise ValueError(f"no opcode for {e.func} in an MMS term")
+        memo[e] = r
+        return r
+    return visit(sy.sympify(expr))
+
+
+VOLUME_DEGREE = 9        # simplex_quadrature(dim, 5), the rule of MMSAssembler, with the test function counted in
+MEMBRANE_DEGREE = 10     # the problem's own q_pts rule
+
+
+def device_source_terms(problem):
+    """The sixteen terms of ``MMSAssembler.rhs_vector`` as step sources, each to be multiplied by dt by the hook
+    (linear_forms.apply_sources).  Host work only.  A list of dicts:
+    ``kind`` 'volume': ``field``, ``expr_i``, ``expr_e`` (two terms, one per side) -- the ions' f_k and, on 'phi', -f_phi (the
+    reference's form carries the minus sign, KNPEMIx_problem.py:646-651, and the hook adds);
+    ``kind`` 'membrane': ``field``, ``side``, ``expr`` -- (1 / (F z_k)) alpha_i^k f_phi_k on 'i' and -(1 / (F z_k)) alpha_e^k
+    (f_phi_k + f_gamma) on 'e' per ion (:622-626), f_phi_m on ('phi', 'i') and -(f_phi_m + f_gamma) on ('phi', 'e') (:650-651), with
+    alpha_r^k = D_r^k z_k^2 k_r^k / sum_j D_r^j z_j^2 k_r^j of the solution Functions ``wh[r][j]`` (the previous step's values)."""
+    p = problem
+    src = p.src_terms
+    memo = {}
+    conv = lambda e: to_fem(e, p, memo)
+    names = [ion["name"] for ion in p.ion_list]
+    terms = [dict(kind="volume", field=nm, expr_i=conv(src[f"f_{nm}_i"]), expr_e=conv(src[f"f_{nm}_e"])) for nm in names]
+    terms.append(dict(kind="volume", field="phi", expr_i=-conv(src["f_phi_i"]), expr_e=-conv(src["f_phi_e"])))
+    F = float(p.F.value)
+    w = [[float(ion["D" + r].value) * float(ion["z"].value) ** 2 for ion in p.ion_list] for r in "ie"]
+    den = []
+    for r in range(2):
+        d = w[r][0] * p.wh[r][0]
+        for j in range(1, p.N_ions):
+            d = d + w[r][j] * p.wh[r][j]
+        den.append(d)
+    fgam, fpm = conv(src["f_gamma"]), conv(src["f_phi_m"])
+    for j, ion in enumerate(p.ion_list):
+        z = float(ion["z"].value)
+        fim = conv(src[f"f_phi_{ion['name']}"])
+        al_i, al_e = w[0][j] * p.wh[0][j] / den[0], w[1][j] * p.wh[1][j] / den[1]
+        terms.append(dict(kind="membrane", field=ion["name"], side="i", expr=(1.0 / (F * z)) * al_i * fim))
+        terms.append(dict(kind="membrane", field=ion["name"], side="e", expr=(-1.0 / (F * z)) * al_e * (fim + fgam)))
+    terms.append(dict(kind="membrane", field="phi", side="i", expr=fpm))
+    terms.append(dict(kind="membrane", field="phi", side="e", expr=-(fpm + fgam)))
+    return terms
+
+
+def register_device_sources(problem):
+    """``device_source_terms`` through ``add_source`` / ``add_membrane_source`` (needs the library context); the handles"""
+    from .linear_forms import add_membrane_source, add_source
+    out = []
+    for tm in problem.mms_source_terms:
+        if tm["kind"] == "volume":
+            out.append(add_source(problem, tm["field"], tm["expr_i"], tm["expr_e"], degree=VOLUME_DEGREE))
+        else:
+            out.append(add_membrane_source(problem, tm["field"], tm["side"], tm["expr"], degree=MEMBRANE_DEGREE))
+    return out
+
+
+def error_integrands(problem):
+    """((integrand_i, integrand_e) of the three concentrations, (integrand_i, integrand_e) of the potential): the squared errors
+    (wh[r][k] - exact_k_r)^2 against the exact solution at the problem's time"""
+    p = problem
+    memo = {}
+    names = [ion["name"] for ion in p.ion_list] + ["phi"]
+    sq = [[(p.wh[r][k] - to_fem(p.exact_sols[f"{nm}_{'ie'[r]}"], p, memo)) ** 2 for k, nm in enumerate(names)] for r in range(2)]
+    n = p.N_ions
+    return (sq[0][:n], sq[1][:n]), (sq[0][n], sq[1][n])
+
+
+class DeviceErrors:
+    """The L2 errors of ``MMSAssembler.l2_errors`` from two volume functionals at ``VOLUME_DEGREE`` (its rule): one with the three
+    concentration errors as outputs, one with the potential error.  A call integrates on the device and reads back one small
+    array per functional (tags x outputs) instead of copying the eight solution fields to the host."""
+
+    def __init__(self, problem):
+        from .functionals import VolumeFunctional
+        conc, pot = error_integrands(problem)
+        self.conc = VolumeFunctional(problem, list(conc[0]), list(conc[1]), degree=VOLUME_DEGREE)
+        self.pot = VolumeFunctional(problem, pot[0], pot[1], degree=VOLUME_DEGREE)
+
+    def __call__(self):
+        """[Na_i, Na_e, K_i, K_e, Cl_i, Cl_e, phi_i, phi_e]"""
+        c, ph = self.conc.value(), self.pot.value()
+        side_c, side_p = np.asarray(self.conc.side), np.asarray(self.pot.side)
+        out = []
+        for k in range(c.shape[1]):
+            out += [math.sqrt(float(c[side_c == s, k].sum())) for s in range(2)]
+        out += [math.sqrt(float(ph[side_p == s, 0].sum())) for s in range(2)]
         return out

@@ -174,6 +174,8 @@ class MixedDimensionalProblem(ABC):
                 self.dim = int(config["MMS_test"]["dim"])
             except Exception:
                 raise RuntimeError('For MMS test, provide dimension "dim" in input file.')
+            # device: true evaluates the analytic sources and the error norms on the device (cgx_hip/mms.py); default: on the host
+            self.mms_device = bool(config["MMS_test"].get("device", False))
         self.source_terms = config.get("source_terms", None)
         if self.source_terms not in (None, "ion_injection"):
             raise RuntimeError(f"Unknown source_terms '{self.source_terms}' (the reference knows 'ion_injection').")
@@ -461,6 +463,9 @@ class MixedDimensionalProblem(ABC):
             return self.backend
         from .backend import Backend
         self.backend = Backend(self)
+        if getattr(self, "mms_source_terms", None) and not getattr(self, "mms_sources", None):
+            from .mms import register_device_sources      # MMS_test with device: true; the terms are setup_variational_form's
+            self.mms_sources = register_device_sources(self)
         return self.backend
 
     def backend_hh_update(self, model):
@@ -472,6 +477,7 @@ class MixedDimensionalProblem(ABC):
     mesh_conversion_factor = 1.0
     fem_order = 1
     MMS_test = False
+    mms_device = False
     dirichlet_bcs = False
     pin_ecs_potential = False
 
@@ -813,6 +819,13 @@ class ProblemKNPEMI(MixedDimensionalProblem):
             fem.compile_state_program(st, roles, self.aux_functions)
         if self.backend is not None and getattr(self.backend, "tag_program", None) != self.tag_program:
             raise RuntimeError("setup_variational_form() changed the membrane-tag -> program map after the backend was created")
+        if self.MMS_test and self.mms_device:
+            # the sixteen extra terms of L (KNPEMIx_problem.py:616-651) as step sources of the device: stated here, registered
+            # with the library context (create_backend)
+            from .mms import device_source_terms, register_device_sources
+            self.mms_source_terms = device_source_terms(self)
+            if self.backend is not None and not getattr(self, "mms_sources", None):
+                self.mms_sources = register_device_sources(self)
         self.a = "hard-wired in knp_kernels.hip (k_assemble_pairs, k_gamma_facets, k_gamma_pairs)"
         self.L = "hard-wired in knp_kernels.hip (k_rhs, k_gamma_facets) + membrane programs"
         if self.backend is not None:
@@ -982,10 +995,16 @@ class ProblemKNPEMI(MixedDimensionalProblem):
 
     def print_errors(self):
         """L2 errors against the exact solution at the current time (KNPEMIx_problem.py:845-907)."""
-        if not hasattr(self, "_mms_asm"):
-            from .mms import MMSAssembler
-            self._mms_asm = MMSAssembler(self)
-        e = self._mms_asm.l2_errors()          # [Na_i, Na_e, K_i, K_e, Cl_i, Cl_e, phi_i, phi_e]
+        if self.mms_device:
+            if not hasattr(self, "_mms_errors"):
+                from .mms import DeviceErrors
+                self._mms_errors = DeviceErrors(self)
+            e = self._mms_errors()             # two volume functionals: one small read-back each
+        else:
+            if not hasattr(self, "_mms_asm"):
+                from .mms import MMSAssembler
+                self._mms_asm = MMSAssembler(self)
+            e = self._mms_asm.l2_errors()      # [Na_i, Na_e, K_i, K_e, Cl_i, Cl_e, phi_i, phi_e]
         self.print("#-------------- ERRORS --------------#")
         for nm, v in zip(("Na_i ", "Na_e ", "K_i  ", "K_e  ", "Cl_i ", "Cl_e ", "phi_i", "phi_e"), e):
             self.print(f"L2 {nm} error:", v)

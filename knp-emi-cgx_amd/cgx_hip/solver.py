@@ -199,9 +199,10 @@ class SolverKNPEMI:
         if async_matrix:
             be.assemble_matrix_async()
         be.assemble_rhs()
-        if p.MMS_test:
+        if p.MMS_test and not p.mms_device:
             # extra terms of L for the manufactured solution (KNPEMIx_problem.py:616-651): host integrals of the
-            # analytic sources, added to the device vector; then the Dirichlet values (bcs= of assemble_vector_block)
+            # analytic sources, added to the device vector; then the Dirichlet values (bcs= of assemble_vector_block).
+            # With MMS_test: device the same terms are registered sources and go through apply_sources below.
             if not hasattr(p, "_mms_asm"):
                 from .mms import MMSAssembler
                 p._mms_asm = MMSAssembler(p)

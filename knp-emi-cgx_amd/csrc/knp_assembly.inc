@@ -265,14 +265,15 @@ int knp_assemble_rhs(knp_ctx* ctx, const knp_fields* fields, double* b) {
     if (g.n_g > 0) {
         // dynamic LDS: register file [n_regs][NT] | constants | code of the block's program
         const int n_regs = std::max(ctx->prog_regs, 1), ccap = (std::max(ctx->prog_consts_cap, 1) + 1) & ~1;   // even: code stays 16-B aligned
-#define GF_LAUNCH(D, L, Q, B, O)                                                                                              \
+#define GF_LAUNCH(D, L, Q, B, O, M)                                                                                            \
     do {                                                                                                                      \
         const size_t lds = ((size_t)n_regs * Q * B + ccap) * sizeof(double) + (size_t)4 * std::max(ctx->prog_len_cap, 1) * sizeof(int32_t); \
         if (lds > 160 * 1024) { ctx->err = "membrane programs need more LDS than a CU has"; return KNP_E_STATE; }             \
-        if (lds != ctx->gamma_lds_set)                                                                                        \
-            HIPCHK(hipFuncSetAttribute((const void*)k_gamma_facets<D, false, true, L, Q, B, O>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+        if (lds != ctx->gamma_lds_set || M != ctx->gamma_lds_funcs)                                                           \
+            HIPCHK(hipFuncSetAttribute((const void*)k_gamma_facets<D, false, true, L, Q, B, O, M>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
         ctx->gamma_lds_set = lds;                                                                                             \
-        hipLaunchKernelGGL((k_gamma_facets<D, false, true, L, Q, B, O>), dim3((unsigned)(((int64_t)g.n_g * L + B - 1) / B)), dim3(B), lds, \
+        ctx->gamma_lds_funcs = M;                                                                                             \
+        hipLaunchKernelGGL((k_gamma_facets<D, false, true, L, Q, B, O, M>), dim3((unsigned)(((int64_t)g.n_g * L + B - 1) / B)), dim3(B), lds, \
                            ctx->stream, g.n_g, g.n_q, P, ctx->d_fv, ctx->d_fmeas, ctx->d_qp, ctx->d_qw, f, n_aux, ctx->d_coords,  \
                            ctx->d_gamma_prog, (const int32_t* const*)ctx->d_prog_code, (const int32_t*)ctx->d_prog_len,         \
                            (const double* const*)ctx->d_prog_consts, (const int32_t*)ctx->d_prog_nconsts, n_regs, ccap,        \
@@ -295,8 +296,11 @@ int knp_assemble_rhs(knp_ctx* ctx, const knp_fields* fields, double* b) {
             void* args[] = {&n_g, &n_q, &Pp, &fv, &fmeas, &qp, &qw, &ff, &n_aux_, &coords, &gp, &pc, &pl, &pk, &pn, &nr, &cc0, &fmat, &fvec};
             const int L = g.dim == 2 ? 8 : many ? 4 : 16;
             HIPCHK(hipModuleLaunchKernel((hipFunction_t)jit, (unsigned)(((int64_t)g.n_g * L + 63) / 64), 1, 1, 64, 1, 1, 0, ctx->stream, args, nullptr));
-        } else if (g.dim == 2) GF_LAUNCH(2, 8, 1, 64, 2);
-        else GF_LAUNCH(3, 16, 3, 64, 2);
+        } else if (g.dim == 2) {
+            if (ctx->prog_funcs) GF_LAUNCH(2, 8, 1, 64, 2, true);
+            else GF_LAUNCH(2, 8, 1, 64, 2, false);
+        } else if (ctx->prog_funcs) GF_LAUNCH(3, 16, 3, 64, 2, true);
+        else GF_LAUNCH(3, 16, 3, 64, 2, false);
 #undef GF_LAUNCH
     }
     FieldPtrs src;

@@ -113,7 +113,7 @@ __global__ void __launch_bounds__(NT) k_diag_cells(int n, const int32_t* __restr
 // (b) integral over the selected membrane facets of the sum of a program's outputs: quadrature points q, weights q_w |F|
 static constexpr int DIAG_BT = 128;   // facets per block: the interpreter's LDS register file is [n_regs][DIAG_BT] doubles
 struct DiagConsts { double v[KNP_DIAG_MAX_CONSTS]; };
-template <int DIM>
+template <int DIM, bool FUNCS = false>
 __global__ void __launch_bounds__(DIAG_BT) k_diag_facets(int n, const int32_t* __restrict__ item, const int32_t* __restrict__ key,
                                                          const int32_t* __restrict__ fv, const double* __restrict__ fmeas, int n_q,
                                                          const double* __restrict__ qp, const double* __restrict__ qw, FieldPtrs f,
@@ -167,7 +167,7 @@ __global__ void __launch_bounds__(DIAG_BT) k_diag_facets(int n, const int32_t* _
             }
             xq[0][d] = t;
         }
-        run_program<1, DIAG_BT>(code, n_instr, sk, kiq, keq, phq, auxq, xq, Iout, reg);
+        run_program<1, DIAG_BT, FUNCS>(code, n_instr, sk, kiq, keq, phq, auxq, xq, Iout, reg);
         acc += qw[q] * meas * (Iout[0][0] + Iout[0][1] + Iout[0][2]);
     }
     diag_chunk_partials<DiagSum<1>, DIAG_BT>(live ? key[i] : -1, live, i == n - 1, DiagSum<1>{{acc}}, partial);
@@ -533,6 +533,7 @@ int knp_diag_set_program(knp_ctx* ctx, int32_t n_instr, const int32_t* code, int
     KCHK(dev_upload_raw(ctx, &ctx->diag_code, code, (size_t)4 * n_instr));
     ctx->diag_n_instr = n_instr;
     ctx->diag_n_regs = n_regs;
+    ctx->diag_funcs = program_uses_funcs(n_instr, code);
     ctx->diag_n_consts = n_consts;
     for (int i = 0; i < n_consts; ++i) ctx->diag_consts[i] = consts[i];
     ctx->diag_prog = true;
@@ -564,9 +565,11 @@ int knp_diag_membrane_integral(knp_ctx* ctx, const knp_fields* fields, double* o
         const size_t lds = (size_t)std::max(ctx->diag_n_regs, 1) * DIAG_BT * sizeof(double);   // <= 48 registers: 48 KiB
         const int n_q = ctx->g.n_q;
         by_dim(ctx->g.dim, [&](auto D) {
-            hipLaunchKernelGGL(k_diag_facets<D()>, dim3(m.n_chunks), dim3(DIAG_BT), lds, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_fv,
-                               ctx->d_fmeas, n_q, ctx->d_qp, ctx->d_qw, f, n_aux, ctx->d_coords, ctx->diag_code, ctx->diag_n_instr, K,
-                               ctx->diag_n_consts, m.d_partial);
+            with_flag(ctx->diag_funcs, [&](auto M) {
+                hipLaunchKernelGGL((k_diag_facets<D(), M()>), dim3(m.n_chunks), dim3(DIAG_BT), lds, ctx->stream, m.n, m.d_item, m.d_key, ctx->d_fv,
+                                   ctx->d_fmeas, n_q, ctx->d_qp, ctx->d_qw, f, n_aux, ctx->d_coords, ctx->diag_code, ctx->diag_n_instr, K,
+                                   ctx->diag_n_consts, m.d_partial);
+            });
         });
         HIPCHK(hipGetLastError());
     }

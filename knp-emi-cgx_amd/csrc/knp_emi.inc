@@ -134,7 +134,7 @@ k_emi_spmv(int n, const int32_t* __restrict__ pair_ptr, const int32_t* __restric
 // (a) one thread per membrane facet: fvec[a * n_g + f] = |F| sum_q w_q lambda_a(q) (C_M phi_m(q) - dt I_ch(q)), I_ch = the sum of
 // the outputs of the facet's program at the point.  The interpreter needs wave-uniform instruction words: every program some lane of
 // the wave uses is run by the whole wave and each lane keeps the value of its own.
-template <int DIM>
+template <int DIM, bool FUNCS = false>
 __global__ void __launch_bounds__(EMI_BT)
 k_emi_facets(int n_g, int n_q, double C_M, double dt, const int32_t* __restrict__ fv, const double* __restrict__ fmeas,
              const double* __restrict__ qp, const double* __restrict__ qw, const double* __restrict__ phim, EmiAux aux, int n_aux,
@@ -180,7 +180,7 @@ k_emi_facets(int n_g, int n_q, double C_M, double dt, const int32_t* __restrict_
         for (int pl = 0; pl < n_progs; ++pl) {
             if (__ballot(prog == pl) == 0) continue;
             double Iout[1][3] = {{0.0, 0.0, 0.0}};
-            run_program<1, EMI_BT>(prog_code[pl], prog_len[pl], prog_consts[pl], kq, kq, phq, auxq, xq, Iout, reg);
+            run_program<1, EMI_BT, FUNCS>(prog_code[pl], prog_len[pl], prog_consts[pl], kq, kq, phq, auxq, xq, Iout, reg);
             if (prog == pl) I = Iout[0][0] + Iout[0][1] + Iout[0][2];
         }
         const double w = qw[q] * meas * (C_M * phq[0] - dt * I);
@@ -441,6 +441,7 @@ static int emi_sync_programs(knp_ctx* ctx) {
     std::vector<double*> consts(np, nullptr);
     std::vector<int32_t> lens(np, 0), ncs(np, 0);
     ctx->prog_regs = ctx->prog_len_cap = ctx->prog_consts_cap = 0;
+    ctx->prog_funcs = false;
     int need = 0;
     for (size_t i = 0; i < ctx->progs.size(); ++i) {
         const KnpProgram& pr = ctx->progs[i];
@@ -449,6 +450,7 @@ static int emi_sync_programs(knp_ctx* ctx) {
         ctx->prog_regs = std::max(ctx->prog_regs, pr.n_regs);
         ctx->prog_len_cap = std::max(ctx->prog_len_cap, pr.n_instr);
         ctx->prog_consts_cap = std::max(ctx->prog_consts_cap, pr.n_consts);
+        ctx->prog_funcs = ctx->prog_funcs || pr.funcs;
         for (int k = 0; k < pr.n_instr; ++k)
             if (pr.h_code[4 * k] == KNP_OP_AUX) need = std::max(need, pr.h_code[4 * k + 2] + 1);
     }
@@ -576,9 +578,12 @@ int knp_emi_assemble_rhs(knp_ctx* ctx, const knp_fields* fields, const double* f
         if (lds > 64 * 1024) { ctx->err = "membrane programs need more LDS than the EMI facet kernel has"; return KNP_E_STATE; }
         const int n_progs = ctx->max_prog + 1;
         with_either<2, 3>(g.dim == 2, [&](auto D) {
-            hipLaunchKernelGGL(k_emi_facets<D()>, dim3(nblocks(g.n_g, EMI_BT)), dim3(EMI_BT), lds, ctx->stream, g.n_g, g.n_q, E.C_M, E.dt, ctx->d_fv,
-                               ctx->d_fmeas, ctx->d_qp, ctx->d_qw, fields->phi_m, aux, n_aux, ctx->d_coords, ctx->d_gamma_prog, n_progs,
-                               (const int32_t* const*)ctx->d_prog_code, (const int32_t*)ctx->d_prog_len, (const double* const*)ctx->d_prog_consts, E.d_fvec);
+            with_flag(ctx->prog_funcs, [&](auto M) {
+                hipLaunchKernelGGL((k_emi_facets<D(), M()>), dim3(nblocks(g.n_g, EMI_BT)), dim3(EMI_BT), lds, ctx->stream, g.n_g, g.n_q, E.C_M, E.dt,
+                                   ctx->d_fv, ctx->d_fmeas, ctx->d_qp, ctx->d_qw, fields->phi_m, aux, n_aux, ctx->d_coords, ctx->d_gamma_prog, n_progs,
+                                   (const int32_t* const*)ctx->d_prog_code, (const int32_t*)ctx->d_prog_len,
+                                   (const double* const*)ctx->d_prog_consts, E.d_fvec);
+            });
         });
     }
     if (n > 0) {

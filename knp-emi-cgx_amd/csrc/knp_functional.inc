@@ -92,7 +92,7 @@ __device__ __forceinline__ void fn_load_fields(const FieldPtrs& f, const FnBind&
 // per live lane, dst = the caller's [n][NOUT]; key is not read.  LOAD: NV x NOUT sums, acc[a][j] += (meas q_w[q] lam[a]) OUT_j in the same
 // order of q, and the end is the store of all of them, dst = the caller's [n][NV][NOUT]: item-major, so that the gather of
 // knp_scatter_apply finds the NOUT numbers of an entry (i, a) side by side; key is not read, and there is no reduction.
-template <int DIM, int NV, int NOUT, FnEnd END>
+template <int DIM, int NV, int NOUT, FnEnd END, bool FUNCS>
 __device__ __forceinline__ void fn_integrate(const FnLane& L, int n, const int32_t* __restrict__ key, const FnValues<NV>& U,
                                              const double (*x)[DIM], const FnBind& B, int n_q, const double* __restrict__ qp,
                                              const double* __restrict__ qw, double meas, const int32_t* __restrict__ code, int n_instr,
@@ -140,7 +140,7 @@ __device__ __forceinline__ void fn_integrate(const FnLane& L, int n, const int32
             }
             xq[0][d] = t;
         }
-        run_program<1, FN_BT>(code, n_instr, L.sk, kiq, keq, phq, auxq, xq, Iout, L.reg);
+        run_program<1, FN_BT, FUNCS>(code, n_instr, L.sk, kiq, keq, phq, auxq, xq, Iout, L.reg);
         const double w = ITEMS ? qw[q] : qw[q] * meas;
         if constexpr (END == FN_LOAD) {
 #pragma unroll
@@ -175,7 +175,7 @@ __device__ __forceinline__ void fn_integrate(const FnLane& L, int n, const int32
 }
 
 // ---- the volume kind's own: the cell load, |T|, grad(lambda) and the derivative slots ---------------------------------------------
-template <int DIM, int NOUT, FnEnd END = FN_TAGS>
+template <int DIM, int NOUT, FnEnd END = FN_TAGS, bool FUNCS = false>
 __global__ void __launch_bounds__(FN_BT) k_functional(int n, const int32_t* __restrict__ item, const int32_t* __restrict__ key,
                                                       const int32_t* __restrict__ cells, const double* __restrict__ coords, int n_q,
                                                       const double* __restrict__ qb, const double* __restrict__ qw, FieldPtrs f, FnBind B,
@@ -223,7 +223,7 @@ __global__ void __launch_bounds__(FN_BT) k_functional(int n, const int32_t* __re
             U.av[k][0] = d;
         }
     }
-    fn_integrate<DIM, DIM + 1, NOUT, END>(L, n, key, U, x, B, n_q, qb, qw, vol, code, n_instr, partial);
+    fn_integrate<DIM, DIM + 1, NOUT, END, FUNCS>(L, n, key, U, x, B, n_q, qb, qw, vol, code, n_instr, partial);
 }
 
 // ---- the plan lifecycle both kinds share.  A kind is its name in the error texts and its table of the context: the ids of the two
@@ -282,6 +282,7 @@ static int fn_create(knp_ctx* ctx, const FnKind& kind, const FnCreateArgs& a, in
         P.aux_mode[k] = (int8_t)a.aux_mode[k];
     }
     KCHK(validate_program(ctx, a.n_instr, a.code, a.n_consts, &P.n_regs));
+    P.funcs = program_uses_funcs(a.n_instr, a.code);
     for (int i = 0; i < a.n_instr; ++i) {       // which slots the code reads; the indices are validate_program's
         const int op = a.code[4 * i], s = a.code[4 * i + 2];
         if (op == KNP_OP_KI) P.need |= FN_KI << s;
@@ -326,8 +327,8 @@ static int fn_set_constants(knp_ctx* ctx, const FnKind& kind, int32_t id, int32_
     return KNP_OK;
 }
 
-// Evaluation of either kind: binds the fields the program reads, then launch(D, NOUT, END, P, f, B, K, lds, dst) is the kind's kernel
-// over the plan's map, and the combines write out.  FN_ITEMS / FN_LOAD (knp_fields.inc): the kernel stores every item's mean, or its
+// Evaluation of either kind: binds the fields the program reads, then launch(D, NOUT, END, M, P, f, B, K, lds, dst) is the kind's kernel
+// over the plan's map (M: its FUNCS instantiation, for a program with KNP_OP_SIN / COS / TANH), and the combines write out.  FN_ITEMS / FN_LOAD (knp_fields.inc): the kernel stores every item's mean, or its
 // load vector, straight into out (dst = out, [n][n_out] or [n][nv][n_out] in the plan's item order) and there is no combine; otherwise
 // dst is the map's partials.
 template <FnEnd END, class Launch>
@@ -363,9 +364,11 @@ static int fn_eval(knp_ctx* ctx, const FnKind& kind, int32_t id, const knp_field
         double* dst = ITEMS ? out : m.d_partial;
         const std::integral_constant<FnEnd, END> items;
         by_dim(ctx->g.dim, [&](auto D) {
-            if (P.n_out == 1) launch(D, std::integral_constant<int, 1>(), items, P, f, B, K, lds, dst);
-            else if (P.n_out == 2) launch(D, std::integral_constant<int, 2>(), items, P, f, B, K, lds, dst);
-            else launch(D, std::integral_constant<int, 3>(), items, P, f, B, K, lds, dst);
+            with_flag(P.funcs, [&](auto M) {
+                if (P.n_out == 1) launch(D, std::integral_constant<int, 1>(), items, M, P, f, B, K, lds, dst);
+                else if (P.n_out == 2) launch(D, std::integral_constant<int, 2>(), items, M, P, f, B, K, lds, dst);
+                else launch(D, std::integral_constant<int, 3>(), items, M, P, f, B, K, lds, dst);
+            });
         });
         HIPCHK(hipGetLastError());
     }
@@ -404,10 +407,10 @@ static bool functional_flat_cell(const std::vector<int32_t>& cells, const std::v
 template <FnEnd END>
 static int functional_eval(knp_ctx* ctx, int32_t id, const knp_fields* fields, double* out) {
     return fn_eval<END>(ctx, fn_volume(ctx), id, fields, out,
-                          [&](auto D, auto NOUT, auto I, const KnpFunctional& P, const FieldPtrs& f, const FnBind& B, const DiagConsts& K, size_t lds,
-                              double* dst) {
+                          [&](auto D, auto NOUT, auto I, auto M, const KnpFunctional& P, const FieldPtrs& f, const FnBind& B, const DiagConsts& K,
+                              size_t lds, double* dst) {
                               const KnpDiagMap& m = P.map;
-                              hipLaunchKernelGGL((k_functional<D(), NOUT(), I()>), dim3(m.n_chunks), dim3(FN_BT), lds, ctx->stream, m.n, m.d_item,
+                              hipLaunchKernelGGL((k_functional<D(), NOUT(), I(), M()>), dim3(m.n_chunks), dim3(FN_BT), lds, ctx->stream, m.n, m.d_item,
                                                  m.d_key, ctx->d_cells, ctx->d_coords, P.n_q, P.d_qp, P.d_qw, f, B, P.d_code, P.n_instr, K,
                                                  P.n_consts, dst);
                           });

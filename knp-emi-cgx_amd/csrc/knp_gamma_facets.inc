@@ -27,7 +27,15 @@ __device__ __forceinline__ double powi_d(double x, int e) {
 // The caller guarantees that every active lane of the wave runs the same program, so the instruction words are
 // wave-uniform: readfirstlane moves them to scalar registers (scalar branch, scalar address arithmetic), and the next
 // instruction is fetched while the current one executes.
-template <int QV, int BT>
+// FUNCS: the instantiation that also knows the function block KNP_OP_SIN / COS / TANH.  A kernel launches it only for a program that
+// holds such an opcode (program_uses_funcs): inlined, the three fp64 functions (Payne-Hanek range reduction) cost every kernel around
+// the interpreter some 19 registers and eleven of them a wave of occupancy, for programs that never call them.  Behind a call the
+// FUNCS kernels keep the registers of their twins, and the kernels without the flag are the ones of before, instruction by instruction.
+__device__ __noinline__ double prog_sin(double x) { return sin(x); }
+__device__ __noinline__ double prog_cos(double x) { return cos(x); }
+__device__ __noinline__ double prog_tanh(double x) { return tanh(x); }
+
+template <int QV, int BT, bool FUNCS = false>
 __device__ __forceinline__ void run_program(const int32_t* code, int n_instr, const double* consts,
                                             const double (*ki)[3], const double (*ke)[3], const double* phim,
                                             const double (*aux)[KNP_MAX_AUX], const double (*xq)[3], double (*Iout)[3], double* reg) {
@@ -92,7 +100,13 @@ __device__ __forceinline__ void run_program(const int32_t* code, int n_instr, co
                 EACH Iout[s_][a] += RG(b, s_); break;
             case KNP_OP_MOV: UN(x);
             case KNP_OP_POWI: UN(powi_d(x, b));
-            default: break;
+            default:
+                if constexpr (FUNCS) {
+                    if (op == KNP_OP_SIN) { EACH RG(d, s_) = prog_sin(RG(a, s_)); }
+                    else if (op == KNP_OP_COS) { EACH RG(d, s_) = prog_cos(RG(a, s_)); }
+                    else if (op == KNP_OP_TANH) { EACH RG(d, s_) = prog_tanh(RG(a, s_)); }
+                }
+                break;
         }
     }
 #undef BIN
@@ -109,7 +123,7 @@ __device__ __forceinline__ void run_program(const int32_t* code, int n_instr, co
 //   fmat[(g*NPK + ab)*6 + k], k = 0..2 intra ions, 3..5 extra ions : M_Gamma[alpha^k C_M/(F z_k)]
 //   fvec[(k*DIM + a)*n_g + g],  k = 0..2 intra, 3..5 extra, 6 potential
 // ------------------------------------------------------------------------------------------
-template <int DIM, bool MAT, bool VEC, int LF, int QV, int BT>
+template <int DIM, bool MAT, bool VEC, int LF, int QV, int BT, bool FUNCS = false>
 __device__ __forceinline__ void
 gamma_facets_body(int n_g, int n_q, DevParams P, const int32_t* __restrict__ fv, const double* __restrict__ fmeas,
                const double* __restrict__ qp, const double* __restrict__ qw, FieldPtrs f, int n_aux,
@@ -272,7 +286,7 @@ gamma_facets_body(int n_g, int n_q, DevParams P, const int32_t* __restrict__ fv,
 #else
             double* reg = smem + threadIdx.x;
             if (code) {
-                run_program<QV, BT>(code, n_instr, consts, kiq, keq, phq, auxq, xq, Iout, reg);
+                run_program<QV, BT, FUNCS>(code, n_instr, consts, kiq, keq, phq, auxq, xq, Iout, reg);
             } else {   // mixed block: serialise over the programs present in this wave (the interpreter needs uniform code)
                 bool pending = true;
                 while (true) {
@@ -280,7 +294,7 @@ gamma_facets_body(int n_g, int n_q, DevParams P, const int32_t* __restrict__ fv,
                     if (!m) break;
                     const int pl = __shfl(prog, __ffsll((long long)m) - 1);
                     if (pending && prog == pl) {
-                        run_program<QV, BT>(prog_code[pl], prog_len[pl], prog_consts[pl], kiq, keq, phq, auxq, xq, Iout, reg);
+                        run_program<QV, BT, FUNCS>(prog_code[pl], prog_len[pl], prog_consts[pl], kiq, keq, phq, auxq, xq, Iout, reg);
                         pending = false;
                     }
                 }
@@ -353,9 +367,9 @@ extern "C" __global__ void __launch_bounds__(64, 1) knp_gamma_vec_3d_many(KNP_GA
 // per point); forcing three or four waves per SIMD spills to scratch memory: 3.06 / 3.70 ms.  KNP_GAMMA_QV=9 keeps the nine-point kernel.
 extern "C" __global__ void __launch_bounds__(64, 2) knp_gamma_vec_3d_q1(KNP_GAMMA_ARGS) { gamma_facets_body<3, false, true, 4, 1, 64>(KNP_GAMMA_PASS); }
 #else
-template <int DIM, bool MAT, bool VEC, int LF, int QV, int BT, int OCC>
+template <int DIM, bool MAT, bool VEC, int LF, int QV, int BT, int OCC, bool FUNCS = false>
 __global__ void __launch_bounds__(BT, OCC) k_gamma_facets(KNP_GAMMA_ARGS) {
-    gamma_facets_body<DIM, MAT, VEC, LF, QV, BT>(KNP_GAMMA_PASS);
+    gamma_facets_body<DIM, MAT, VEC, LF, QV, BT, FUNCS>(KNP_GAMMA_PASS);
 }
 #endif
 

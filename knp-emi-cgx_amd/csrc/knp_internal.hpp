@@ -90,6 +90,7 @@ struct KnpStateProg {
     int kind = 0;                    // 0 gate (OUT 0 = alpha, OUT 1 = beta), 1 general (OUT 0 = dy/dt)
     int aux_index = -1;              // the aux slot under which the programs read this state
     int n_regs = 0;
+    bool funcs = false;              // holds KNP_OP_SIN / COS / TANH
     bool uses_k = false;             // reads a concentration (KNP_OP_KI / KNP_OP_KE)
     std::vector<int32_t> code;       // [n_instr*4]
     std::vector<double> consts;      // travel as kernel arguments of the next knp_state_update
@@ -129,6 +130,7 @@ struct KnpSamplePlan {
 struct KnpFunctional {
     bool live = false;
     int n_q = 0, n_out = 0, n_instr = 0, n_regs = 0, n_consts = 0;
+    bool funcs = false;            // the code holds KNP_OP_SIN / COS / TANH: evaluated by the FUNCS instantiation of the kernel
     unsigned need = 0;             // the field slots the code reads (FN_* bits) and, on a membrane plan, the cells whose geometry it needs
     int8_t aux_mode[KNP_MAX_AUX] = {-1, -1, -1, -1, -1, -1, -1, -1};   // per aux slot: -1 value, 0..2 d/dx_a; a membrane plan also 3..5
                                    // d/dx_a on the '-' cell, 6 / 7 d/dn, 8.. normal component
@@ -161,6 +163,7 @@ struct KnpProjection {
 // ---- device-side program ------------------------------------------------------------------
 struct KnpProgram {
     int n_instr = 0, n_consts = 0, n_regs = 0;
+    bool funcs = false;           // holds an opcode of the function block (KNP_OP_SIN..): the interpreter kernels take their FUNCS twin
     int32_t* d_code = nullptr;
     double* d_consts = nullptr;
     double* h_consts = nullptr;   // pinned staging copy of the constants (per-step refresh without a synchronisation)
@@ -368,6 +371,7 @@ struct knp_ctx {
     int32_t* d_prog_nconsts = nullptr;
     int prog_regs = 0, prog_len_cap = 0, prog_consts_cap = 0;   // maxima over the programs (LDS sizing of k_gamma_facets)
     size_t gamma_lds_set = 0;
+    bool prog_funcs = false, gamma_lds_funcs = false;   // some membrane program holds KNP_OP_SIN..; the instantiation gamma_lds_set was set on
     // run-time compiled membrane kernel (knp_jit.cpp); null: the interpreter runs
     void* jit_module = nullptr;
     void* jit_fn[3] = {nullptr, nullptr, nullptr};   // [0] 2D, [1] 3D right-hand-side facet kernel, [2] 3D with 4 lanes x 9 points per facet
@@ -488,6 +492,7 @@ struct knp_ctx {
     KnpDiagMap diag_act;
     int32_t* diag_code = nullptr;
     int diag_n_instr = 0, diag_n_regs = 0, diag_n_consts = 0;
+    bool diag_funcs = false;
     double diag_consts[KNP_DIAG_MAX_CONSTS] = {};   // host copy: passed to the kernel by value at every launch
     bool diag_prog = false;
     KnpEmi emi;

@@ -107,6 +107,9 @@ bool emit_statement(std::ostringstream& o, int op, int d, int a, int b) {
         case KNP_OP_OUT: o << "I[" << a << "] += " << B << ";"; break;
         case KNP_OP_MOV: o << D << " = " << A << ";"; break;
         case KNP_OP_POWI: o << D << " = powi_d(" << A << ", " << b << ");"; break;
+        case KNP_OP_SIN: o << D << " = sin(" << A << ");"; break;
+        case KNP_OP_COS: o << D << " = cos(" << A << ");"; break;
+        case KNP_OP_TANH: o << D << " = tanh(" << A << ");"; break;
         default: return false;
     }
     return true;
@@ -118,6 +121,7 @@ void sources(int op, int d, int a, int b, int out[3], int& n) {
     switch (op) {
         case KNP_OP_CONST: case KNP_OP_KI: case KNP_OP_KE: case KNP_OP_PHIM: case KNP_OP_AUX: case KNP_OP_X: break;
         case KNP_OP_NEG: case KNP_OP_LN: case KNP_OP_EXP: case KNP_OP_SQRT: case KNP_OP_ABS: case KNP_OP_NOT: case KNP_OP_MOV: case KNP_OP_POWI:
+        case KNP_OP_SIN: case KNP_OP_COS: case KNP_OP_TANH:
             out[n++] = a; break;
         case KNP_OP_OUT: out[n++] = b; break;
         case KNP_OP_SEL: out[n++] = a; out[n++] = b; out[n++] = d; break;

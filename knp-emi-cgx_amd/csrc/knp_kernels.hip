@@ -3238,6 +3238,13 @@ int knp_set_params(knp_ctx* ctx, double dt, double F, double C_M, double psi, in
     return KNP_OK;
 }
 
+// does the program hold an opcode of the function block: then its kernel is the FUNCS instantiation (run_program)
+static bool program_uses_funcs(int n_instr, const int32_t* code) {
+    for (int i = 0; i < n_instr; ++i)
+        if (code[4 * i] >= KNP_OP_SIN && code[4 * i] <= KNP_OP_TANH) return true;
+    return false;
+}
+
 static int validate_program(knp_ctx* ctx, int n_instr, const int32_t* code, int n_consts, int* n_regs_out) {
     int max_reg = -1;
     for (int i = 0; i < n_instr; ++i) {
@@ -3251,7 +3258,7 @@ static int validate_program(knp_ctx* ctx, int n_instr, const int32_t* code, int 
             case KNP_OP_AUX: ok = regok(d) && a >= 0 && a < KNP_MAX_AUX; break;
             case KNP_OP_X: ok = regok(d) && a >= 0 && a < ctx->g.dim; break;
             case KNP_OP_NEG: case KNP_OP_LN: case KNP_OP_EXP: case KNP_OP_SQRT: case KNP_OP_ABS: case KNP_OP_NOT:
-            case KNP_OP_MOV: case KNP_OP_POWI: ok = regok(d) && regok(a); break;
+            case KNP_OP_MOV: case KNP_OP_POWI: case KNP_OP_SIN: case KNP_OP_COS: case KNP_OP_TANH: ok = regok(d) && regok(a); break;
             case KNP_OP_OUT: ok = a >= 0 && a < 3 && regok(b); break;
             default: ok = (op >= KNP_OP_ADD && op <= KNP_OP_SEL) && regok(d) && regok(a) && regok(b); break;
         }
@@ -3269,6 +3276,7 @@ int knp_set_program(knp_ctx* ctx, int32_t id, int32_t n_instr, const int32_t* co
     if ((int)ctx->progs.size() <= id) ctx->progs.resize(id + 1);
     KnpProgram& p = ctx->progs[id];
     p.n_regs = n_regs;
+    p.funcs = program_uses_funcs(n_instr, code);
     HIPCHK(hipStreamSynchronize(ctx->stream));
     dev_free(p.d_code); dev_free(p.d_consts);
     if (p.h_consts) { (void)hipHostFree(p.h_consts); p.h_consts = nullptr; }
@@ -3300,9 +3308,11 @@ static int sync_program_table(knp_ctx* ctx) {
     std::vector<double*> consts(np, nullptr);
     std::vector<int32_t> lens(np, 0), ncs(np, 0);
     ctx->prog_regs = ctx->prog_len_cap = ctx->prog_consts_cap = 0;
+    ctx->prog_funcs = false;
     for (size_t i = 0; i < ctx->progs.size(); ++i) {
         const KnpProgram& pr = ctx->progs[i];
         codes[i] = pr.d_code; consts[i] = pr.d_consts; lens[i] = pr.n_instr; ncs[i] = pr.n_consts;
+        ctx->prog_funcs = ctx->prog_funcs || pr.funcs;
         ctx->prog_regs = std::max(ctx->prog_regs, pr.n_regs);
         ctx->prog_len_cap = std::max(ctx->prog_len_cap, pr.n_instr);
         ctx->prog_consts_cap = std::max(ctx->prog_consts_cap, pr.n_consts);

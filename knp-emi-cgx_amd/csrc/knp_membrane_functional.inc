@@ -24,7 +24,7 @@ static constexpr int MF_DN_I = 6, MF_DN_E = 7, MF_NORMAL = FN_NORMAL;      // sl
 static inline bool mf_mode_ext(int m) { return (m >= 3 && m < MF_DN_I) || m == MF_DN_E; }            // reads the extracellular cell
 static inline bool mf_mode_int(int m) { return (m >= 0 && m < 3) || m == MF_DN_I || m == MF_DN_E || m >= MF_NORMAL; }   // the normal is the intracellular cell's
 
-template <int DIM, int NOUT, FnEnd END = FN_TAGS>
+template <int DIM, int NOUT, FnEnd END = FN_TAGS, bool FUNCS = false>
 __global__ void __launch_bounds__(FN_BT) k_membrane_functional(int n, const int32_t* __restrict__ item, const int32_t* __restrict__ key,
                                                                const int4* __restrict__ rec, const double* __restrict__ fmeas,
                                                                const double* __restrict__ coords, int n_q, const double* __restrict__ qp,
@@ -114,7 +114,7 @@ __global__ void __launch_bounds__(FN_BT) k_membrane_functional(int n, const int3
             U.av[k][0] = d;
         }
     }
-    fn_integrate<DIM, DIM, NOUT, END>(L, n, key, U, x, B, n_q, qp, qw, meas, code, n_instr, partial);
+    fn_integrate<DIM, DIM, NOUT, END, FUNCS>(L, n, key, U, x, B, n_q, qp, qw, meas, code, n_instr, partial);
 }
 
 // the records of k_membrane_functional for the facets of a map, in map order; counts the facets whose extracellular cell does not hold
@@ -155,10 +155,10 @@ static void membrane_functional_records(const KnpHostGraph& g, const std::vector
 template <FnEnd END>
 static int membrane_functional_eval(knp_ctx* ctx, int32_t id, const knp_fields* fields, double* out) {
     return fn_eval<END>(ctx, fn_membrane(ctx), id, fields, out,
-                          [&](auto D, auto NOUT, auto I, const KnpFunctional& P, const FieldPtrs& f, const FnBind& B, const DiagConsts& K, size_t lds,
-                              double* dst) {
+                          [&](auto D, auto NOUT, auto I, auto M, const KnpFunctional& P, const FieldPtrs& f, const FnBind& B, const DiagConsts& K,
+                              size_t lds, double* dst) {
                               const KnpDiagMap& m = P.map;
-                              hipLaunchKernelGGL((k_membrane_functional<D(), NOUT(), I()>), dim3(m.n_chunks), dim3(FN_BT), lds, ctx->stream, m.n,
+                              hipLaunchKernelGGL((k_membrane_functional<D(), NOUT(), I(), M()>), dim3(m.n_chunks), dim3(FN_BT), lds, ctx->stream, m.n,
                                                  m.d_item, m.d_key, reinterpret_cast<const int4*>(P.d_rec), ctx->d_fmeas, ctx->d_coords, P.n_q,
                                                  P.d_qp, P.d_qw, f, B, P.d_code, P.n_instr, K, P.n_consts, dst);
                           });

@@ -26,7 +26,7 @@ struct StateArgs {
     int32_t code_off[KNP_MAX_AUX], n_instr[KNP_MAX_AUX], const_off[KNP_MAX_AUX], kind[KNP_MAX_AUX], aux_index[KNP_MAX_AUX];
 };
 
-template <int DIM>
+template <int DIM, bool FUNCS = false>
 __global__ void __launch_bounds__(STATE_BT) k_state_update(int count, int n_states, int n_iter, StateArgs S, const double* __restrict__ phim,
                                                            int use_k, const double* __restrict__ coords, const int32_t* __restrict__ code,
                                                            int total_instr, int total_consts, int n_regs, double dt, double dto,
@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(STATE_BT) k_state_update(int count, int n_stat
         for (int s = 0; s < n_states; ++s) {
             if (it > 0 && S.kind[s] == 0) continue;      // a gate's rates are those of the start of the step
             Iout[0][0] = Iout[0][1] = Iout[0][2] = 0.0;
-            run_program<1, STATE_BT>(scode + 4 * S.code_off[s], S.n_instr[s], sk + S.const_off[s], kiq, keq, phq, auxq, xq, Iout, reg);
+            run_program<1, STATE_BT, FUNCS>(scode + 4 * S.code_off[s], S.n_instr[s], sk + S.const_off[s], kiq, keq, phq, auxq, xq, Iout, reg);
 #pragma unroll
             for (int j = 0; j < KNP_MAX_AUX; ++j)
                 if (j == s) { o0[j] = Iout[0][0]; o1[j] = Iout[0][1]; }
@@ -140,6 +140,7 @@ int knp_state_set_program(knp_ctx* ctx, int32_t slot, int32_t kind, int32_t aux_
     p.aux_index = aux_index;
     p.n_regs = n_regs;
     p.uses_k = false;
+    p.funcs = program_uses_funcs(n_instr, code);
     for (int i = 0; i < n_instr; ++i) p.uses_k = p.uses_k || code[4 * i] == KNP_OP_KI || code[4 * i] == KNP_OP_KE;
     p.code.assign(code, code + (size_t)4 * n_instr);
     p.consts.assign(consts, consts + n_consts);
@@ -171,7 +172,7 @@ int knp_state_update(knp_ctx* ctx, const knp_fields* fields, double* const* stat
     if (substeps < 1 || !(dt > 0)) { ctx->err = "bad state_update arguments (dt > 0, substeps >= 1)"; return KNP_E_ARG; }
     StateArgs S;
     std::memset(&S, 0, sizeof(S));
-    bool use_k = false, any_general = false;
+    bool use_k = false, any_general = false, funcs = false;
     int n_regs = 1, total_instr = 0, total_consts = 0;
     for (int k = 0; k < KNP_MAX_AUX; ++k) S.aux[k] = fields->aux[k];
     for (int s = 0; s < n_states; ++s) {
@@ -189,6 +190,7 @@ int knp_state_update(knp_ctx* ctx, const knp_fields* fields, double* const* stat
         total_consts += (int)p.consts.size();
         n_regs = std::max(n_regs, p.n_regs);
         use_k = use_k || p.uses_k;
+        funcs = funcs || p.funcs;
         any_general = any_general || p.kind == 1;
     }
     if (use_k)
@@ -212,9 +214,11 @@ int knp_state_update(knp_ctx* ctx, const knp_fields* fields, double* const* stat
     ProfScope ps(ctx, 4);
     const unsigned nb = (unsigned)((count + STATE_BT - 1) / STATE_BT);
     by_dim(ctx->g.dim, [&](auto D) {
-        hipLaunchKernelGGL(k_state_update<D()>, dim3(nb), dim3(STATE_BT), lds, ctx->stream, count, n_states, n_iter, S, fields->phi_m,
-                           use_k ? 1 : 0, ctx->d_coords, st.d_code, total_instr, total_consts, n_regs, dt, dt / substeps,
-                           rush_larsen ? 1 : 0);
+        with_flag(funcs, [&](auto M) {
+            hipLaunchKernelGGL((k_state_update<D(), M()>), dim3(nb), dim3(STATE_BT), lds, ctx->stream, count, n_states, n_iter, S, fields->phi_m,
+                               use_k ? 1 : 0, ctx->d_coords, st.d_code, total_instr, total_consts, n_regs, dt, dt / substeps,
+                               rush_larsen ? 1 : 0);
+        });
     });
     HIPCHK(hipGetLastError());
     return KNP_OK;
